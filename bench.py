@@ -14,7 +14,12 @@ read back (the full decode, nothing skipped). N GPUs: one process per GPU, each 
 axis 0 (each rank decodes the inner chunks its slab touches) and gathered to rank 0 over RCCL
 inside the timed step (C4).
 
-Prints ONE JSON line (rank 0). Extra objects:
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times --steps steps and prints the
+headline figure (value, ms_per_step = wall milliseconds of one timed step); --dump-outputs DIR also
+writes the arrays the last timed step decoded as DIR/<name>.npy (float32, a fixed seeded sample of
+a large array; the inputs are seeded, so two builds run with the same arguments are comparable
+output for output). --full runs everything else after the timed steps (the round-trip check, the
+secondary workloads C3 and C5, the rank shares) and adds these objects to the line:
   roofline      dominant kernel: algorithmic bytes per launch / device time per launch (HIP events on
                 the stream the library launches on), against 8.0 TB/s HBM3E; traffic = HBM bytes
                 per launch from rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE) of this same script
@@ -117,7 +122,7 @@ class C2:
                                    "[transpose{order:[2,1,0]}, bytes{endian:big}], device-resident",
                        "chunks_per_gpu": self.n_chunks, "array_shape_per_gpu": self.shape,
                        "parallelism": f"chunk-partitioned x{world}"}
-        self.data = "synthetic (uniform [-1,1) f32, encoded on device; decode(encode(x)) == x checked)"
+        self.data = "synthetic (uniform [-1,1) f32, encoded on device; decode(encode(x)) == x checked by --full)"
         self.scaling = "weak"
 
     @classmethod
@@ -321,7 +326,7 @@ class C1:
         self.config = {"workload": "C1: round trip (encode + decode) of one 256^3 f32 chunk, [bytes{endian:little}], "
                                    "device-resident store", "chunk_shape": self.shape,
                        "parallelism": f"one chunk per GPU x{world}"}
-        self.data = "synthetic (uniform [-1,1) f32 on device; decode(encode(x)) == x checked)"
+        self.data = "synthetic (uniform [-1,1) f32 on device; decode(encode(x)) == x checked by --full)"
         self.scaling = "weak"
 
     def pre_step(self, sp):
@@ -453,7 +458,7 @@ class C3:
         if world > 1:
             self.config["boxes_this_gpu"] = [[list(b0), list(bs)] for b0, bs in self.boxes]
         self.data = ("synthetic (round(256*(sin(.05x)+cos(.03y)+.5sin(.07z))+N(0,1))/256 f32, shards "
-                     "written by tools/synth; decode(encode(x)) == x checked on device)")
+                     "written by tools/synth; decode(encode(x)) == x checked by --full on device)")
         self.scaling = "strong"
 
     def _box_slab(self, boxes):
@@ -940,7 +945,7 @@ class C5:
                        "encoded_bytes_this_gpu": enc_total,
                        "parallelism": f"LPT chunk partition x{world}"}
         self.data = ("synthetic (background 100 + 64 Gaussian blobs amplitude <= 4000 + sqrt(mean)*N(0,1) noise, "
-                     "u16, seed 42; 2x2x2 mean pyramid; decode(encode(x)) == x checked on device)")
+                     "u16, seed 42; 2x2x2 mean pyramid; decode(encode(x)) == x checked by --full on device)")
         self.scaling = "strong"
         # N > 1: one cross-GPU L0 subset gathered to rank 0 in every step: the middle
         # [64, H/2, W/2] box of L0, whose chunks the LPT partition spreads over the ranks
@@ -1286,7 +1291,7 @@ class Blosc:
                        "chunks_per_gpu": len(idxs), "blosc_ratio": round(self.decoded_bytes / enc_total, 3),
                        "parallelism": f"chunk-partitioned x{world}"}
         self.data = ("synthetic (100 + 900|sin z cos y sin x| + sqrt-scaled N(0,1) noise, u16, seed 42; "
-                     "encoded by c-blosc 1.21; decode(encode(x)) == x checked on device)")
+                     "encoded by c-blosc 1.21; decode(encode(x)) == x checked by --full on device)")
         self.scaling = "weak"
 
     def after_decode(self):
@@ -1504,6 +1509,40 @@ def rank_share_report(rank_ms, n1_ms, step_bytes, gather_bytes, gather_ms, note)
 
 
 # ------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 48 << 20  # all of --dump-outputs' arrays together (float32), under the 64 MB they may take
+
+
+def _step_outputs(W):
+    """(name, device tensor) of every array a step decodes into: what a caller of the timed path holds
+    after it (C4's root: the gathered subset, which its own boxes are decoded into in place)."""
+    if hasattr(W, "outs"):
+        return [(f"level{i}", o) for i, o in enumerate(W.outs)]
+    full = getattr(W, "full", None)
+    return [("out", W.out if full is None else full)]
+
+
+def dump_outputs(W, path):
+    """--dump-outputs: the step's output arrays as path/<name>.npy, float32 (exact for the f32 and u16
+    workloads), in the array's shape. An array over its share of DUMP_BUDGET_BYTES is written as a 1-D
+    sample: the elements at flat indices drawn once from a generator seeded with 0, in index order, so
+    two builds run with the same arguments write the same elements."""
+    arrays = _step_outputs(W)
+    cap = DUMP_BUDGET_BYTES // 4 // len(arrays)
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays:
+        if t.dtype == torch.uint16:
+            t = t.view(torch.int16)
+        if t.numel() > cap:
+            g = torch.Generator()
+            g.manual_seed(0)
+            idx = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.cpu().numpy()
+        if a.dtype == np.int16:  # the u16 workloads' arrays (held as int16 on the device)
+            a = a.view(np.uint16)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+
+
 def world_info(world, dev):
     """The process world this line was measured in: backend, size and every rank's device (gathered
     over the process group at N > 1)."""
@@ -1634,7 +1673,10 @@ def run_gpu(args, rank, world, dev):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    ok = W.check()  # decode(encode(x)) == x, bit for bit, at full size
+    ok = W.check() if args.full else None  # decode(encode(x)) == x, bit for bit, at full size
+    if args.dump_outputs:  # what is written below is what the timed steps decode, not the warm-up's
+        for _, o in _step_outputs(W):
+            (o.view(torch.int16) if o.dtype == torch.uint16 else o).zero_()
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -1645,12 +1687,18 @@ def run_gpu(args, rank, world, dev):
     if world > 1:
         torch.distributed.barrier()
     elapsed = time.perf_counter() - t0
-    if args.child:  # rocprofv3 --pmc pass: only the dispatches matter
+    if args.dump_outputs and rank == 0:
+        dump_outputs(W, args.dump_outputs)
+    if args.child or not args.full:
         for plan, _, _ in plans:
             lib.zgpu_plan_destroy(plan)
         if group:
             group.close()
-        return None
+        if args.child:  # rocprofv3 --pmc pass: only the dispatches matter
+            return None
+        # a plain run: the timed steps and nothing after them
+        gather = W.gather_stats() if hasattr(W, "gather_stats") else None
+        return dict(W=W, elapsed=elapsed, ok=None, world_info=world_info(world, dev), gather=gather)
     # Device time of one decode launch sequence, HIP events on the stream the library launches on;
     # enqueue-only executes (status=NULL), back to back.
     ev0 = torch.cuda.Event(enable_timing=True)
@@ -1734,6 +1782,7 @@ def secondary_legs(args, rank, world, dev, r_primary):
         a.lane_priorities, a.serial_lanes, a.lane_times, a.fork = "", False, False, False
         a.lits_first = None
         a.bench_lanes = args.bench_lanes
+        a.full, a.dump_outputs = True, ""
         gc.collect()
         torch.cuda.empty_cache()
         args.ctx.release_cached()  # the previous leg's pooled device / pinned blocks back to the driver
@@ -1961,10 +2010,19 @@ def main():
                     help="C5 scale of the secondary leg (L0 y/x divided by this)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="print the launcher command --gpus N > 1 would start, and exit (no GPU touched)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the line can report: the round-trip check, "
+                         "the roofline (HIP-event launches, rocprofv3 PMC passes), the CPU baseline, the host / "
+                         "encode / drop-in legs, the rank shares and the secondary workloads")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write the arrays the last step decoded as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of an output larger than the 64 MB the files may take in all)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # N processes, one per GPU: started here as a child launcher BEFORE anything touches the GPU
@@ -1994,6 +2052,25 @@ def main():
     t = float(elapsed.item())
     value = W.step_bytes * args.steps / t / 2 ** 30
     gather = gather_report(r, world, dev)
+    if not args.full:  # a plain run: the headline figure of the timed steps, nothing measured beside it
+        if rank == 0:
+            line = {"metric": METRIC, "value": round(value, 2), "unit": "GiB/s", "n_gpus": world,
+                    "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(t / args.steps * 1e3, 4),
+                    "higher_is_better": True, "scaling": W.scaling, "vs_baseline": None, "dtype": W.dtype,
+                    "data": W.data, "config": W.config, "roundtrip_ok": None, "world": r["world_info"],
+                    "hip_env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", "unset (HIP default: 4)")},
+                    "full": False}
+            if gather:
+                line["gather"] = gather
+            print(json.dumps(line), flush=True)
+        r["W"] = W = None
+        import gc
+        gc.collect()
+        args.ctx.close()
+        torch.cuda.synchronize()
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     cpu = W.cpu_baseline() if (rank == 0 and not args.no_cpu) else None
     share = None
     if args.workload in ("c3", "c5") and world == 1 and args.rank_share and not args.emulate_rank:
@@ -2034,6 +2111,7 @@ def main():
             "decode_batch_ms_incl_host_planning": round(r["batch_ms"], 3),
             "host_leg": r["host"],
             "hip_env": {"GPU_MAX_HW_QUEUES": os.environ.get("GPU_MAX_HW_QUEUES", "unset (HIP default: 4)")},
+            "full": True,
         }
         if r["counters"][L_CTR_ZSTD_SERIAL] or r["counters"][L_CTR_ZSTD_PARALLEL]:
             line["zstd_items_per_step"] = {"block_parallel": r["counters"][L_CTR_ZSTD_PARALLEL],

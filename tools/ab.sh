@@ -14,7 +14,7 @@ for rep in 1 2; do
     # environment variable set
     lib=""; ev=""
     case "$v" in base) ;; *=*) ev=$v ;; *) lib=zarrs_amd/lib_variants/$v/libzgpu.so ;; esac
-    ( [ -n "$ev" ] && export "$ev"; ZGPU_LIB=$lib timeout -k 10 400 python -u bench.py --workload "$W" --no-cpu \
+    ( [ -n "$ev" ] && export "$ev"; ZGPU_LIB=$lib timeout -k 10 400 python -u bench.py --full --workload "$W" --no-cpu \
       --no-pmc --no-host-leg --secondary= --steps "$N" --warmup 2 ) > "$O/$v.$rep.json" 2> "$O/$v.$rep.err" \
       || { echo "$v rc=$?"; tail -5 "$O/$v.$rep.err"; exit 1; }
     python3 -c "import json,sys; d=json.load(open('$O/$v.$rep.json')); print('$v', $rep, d['value'], d['unit'], d['ms_per_step'], 'ms', 'ok' if d['roundtrip_ok'] else 'MISMATCH')"

@@ -4,14 +4,14 @@
 # Steps run in order, each under its own time limit; the session stops at the first failure.
 #   test[:EXPR[:ENV]]    pytest -m gpu (-k EXPR when given; ENV: NAME=VALUE settings, comma-separated)
 #   smoke                __graft_entry__.smoke()
-#   bench:W[:FLAGS[:ENV]] bench.py --workload W, the full line (CPU baseline, PMC passes, host leg);
+#   bench:W[:FLAGS[:ENV]] bench.py --full --workload W, the full line (CPU baseline, PMC passes, host leg);
 #                        FLAGS: extra bench flags, comma-separated (e.g. bench:c5:--c5-scale,2); ENV:
 #                        NAME=VALUE settings, comma-separated
-#   quick:W[:FLAGS]      bench.py --workload W without PMC passes / host leg, short CPU baseline
+#   quick:W[:FLAGS]      bench.py --full --workload W without PMC passes / host leg, short CPU baseline
 #   prof:W[:FLAGS]       rocprofv3 --kernel-trace --stats of bench.py --workload W (5 steps)
 #   serial:W[:FLAGS]     the same with every plan on one stream (--serial-lanes: per-kernel split)
 #   pmc:W:CTR[:FLAGS]    one rocprofv3 --pmc pass (a single counter) of bench.py --workload W
-#   torchrun:N[:FLAGS]   bench.py --gpus N through torch.distributed.run (N processes)
+#   torchrun:N[:FLAGS]   bench.py --gpus N --full through torch.distributed.run (N processes)
 #   lab:BIN:ARGS[:ENV]   tools/labbin/BIN with ARGS (comma-separated) and ENV (NAME=VALUE, comma-separated)
 #   py:SCRIPT[:ARGS]     python3 SCRIPT with ARGS (comma-separated), e.g. a tools/*.py measurement
 # Everything lands in gpurun_out/<tag>/ (step-numbered files).
@@ -38,7 +38,7 @@ for step in "$@"; do
         || { rc=$?; echo "smoke rc=$rc"; tail -20 "$O/$i.smoke.log"; exit $rc; }
       tail -1 "$O/$i.smoke.log" ;;
     bench|quick)
-      F=(${b//,/ }); E=(${c//,/ }); [ "$kind" = quick ] && F+=(--no-pmc --no-host-leg --cpu-seconds 5 --secondary=)
+      F=(--full ${b//,/ }); E=(${c//,/ }); [ "$kind" = quick ] && F+=(--no-pmc --no-host-leg --cpu-seconds 5 --secondary=)
       env "${E[@]}" timeout -k 10 900 python -u bench.py --workload "$a" "${F[@]}" > "$O/$i.bench_$a.json" 2> "$O/$i.bench_$a.err" \
         || { rc=$?; echo "bench rc=$rc"; tail -20 "$O/$i.bench_$a.err"; exit $rc; }
       cat "$O/$i.bench_$a.json" ;;
@@ -58,7 +58,7 @@ for step in "$@"; do
     torchrun)
       F=(${b//,/ })
       timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$a" --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --gpus "$a" --no-pmc --no-host-leg "${F[@]}" > "$O/$i.torchrun.json" \
+        --master-port 29517 bench.py --gpus "$a" --full --no-pmc --no-host-leg "${F[@]}" > "$O/$i.torchrun.json" \
         2> "$O/$i.torchrun.err" || { rc=$?; echo "torchrun rc=$rc"; tail -20 "$O/$i.torchrun.err"; exit $rc; }
       tail -1 "$O/$i.torchrun.json" ;;
     lab)
