@@ -129,8 +129,10 @@ const char *zgpu_version(void);
  *  codecs_json : the Zarr V3 "codecs" JSON array (nested sharding_indexed configs included).
  *                Supported: transpose, bytes, sharding_indexed (nested to any depth, with codecs
  *                around the inner shardings and bytes->bytes codecs after any of them),
- *                crc32c (+numcodecs.crc32c), gzip, zstd, numcodecs.shuffle, blosc (blosclz, lz4,
- *                lz4hc, zlib, snappy, zstd; shuffle / bitshuffle). Others -> ZGPU_UNSUPPORTED.
+ *                crc32c (+numcodecs.crc32c), numcodecs.adler32 (location start, the default, or
+ *                end), numcodecs.fletcher32, gzip, numcodecs.zlib, zstd, numcodecs.shuffle, blosc
+ *                (blosclz, lz4, lz4hc, zlib, snappy, zstd; shuffle / bitshuffle). Others ->
+ *                ZGPU_UNSUPPORTED.
  *  data_type   : Zarr V3 data type name ("float32", "uint16", ...); fixed-size types only.
  *  fill        : native-endian fill value bytes (FillValue::as_ne_bytes), fill_len == dtype size.
  *  validate_checksums : CodecOptions::validate_checksums (zarrs default true, options.rs:24-33).
@@ -382,7 +384,8 @@ int zgpu_retrieve_array_subset_files(zgpu_chain *chain, uint32_t ndim, const uin
 /*
  * Write path: CodecChain::encode (zarrs/src/array/codec/array_to_bytes/
  * codec_chain.rs:528-555) for fixed-size chains -- transpose, bytes (endianness), numcodecs.shuffle
- * (innermost, elementsize = data type size), crc32c (end or start, any number). Compressing codecs
+ * (innermost, elementsize = data type size), crc32c / numcodecs.adler32 (end or start) and
+ * numcodecs.fletcher32, any number of them. Compressing codecs
  * and sharding_indexed return ZGPU_UNSUPPORTED here: they go through zgpu_encode_chunks.
  * zgpu_chain_encoded_size: encoded bytes of one chunk of chunk_shape (BytesRepresentation::FixedSize),
  * -1 if the chain's encoded size is not fixed.
@@ -404,19 +407,20 @@ int zgpu_encode_batch(zgpu_chain *chain, uint32_t ndim, const uint64_t *chunk_sh
  * zgpu_encode_batch plus the variable-length chains: gzip (one DEFLATE stream of dynamic-Huffman or
  * stored blocks in a gzip member, k_gzip_encode), zstd (one single-segment frame of 64 KiB blocks:
  * Huffman / RLE / raw literals, predefined-FSE sequences, optional XXH64 content checksum; encoded in
- * 1 MiB segments, one wave each, k_zstd_encode_seg + k_zstd_frame), crc32c around them,
+ * 1 MiB segments, one wave each, k_zstd_encode_seg + k_zstd_frame), numcodecs.zlib (the same DEFLATE
+ * stream in an RFC 1950 wrapper with its Adler-32 trailer), crc32c / adler32 / fletcher32 around them,
  * the fixed-size stages in front, and sharding_indexed over a fixed-size or compressing inner chain
  * (ShardingCodecBound::encode_bounded, sharding_codec.rs:924-1085, with SubchunkWriteOrder::C: inner
  * chunks in C order of the inner grid, an inner chunk equal to the fill value everywhere omitted,
  * index bytes{endian} + crc32c at the start or end). The compressed bytes are valid streams that
- * every gzip / zstd decoder reads back to the input; they are not byte-identical to zlib's or
- * libzstd's output (the Zarr specification fixes the decoded bytes, not the encoder). blosc
+ * every gzip / zlib / zstd decoder reads back to the input; they are not byte-identical to zlib's,
+ * flate2's or libzstd's output (the Zarr specification fixes the decoded bytes, not the encoder). blosc
  * (BloscCodec::encode, blosc_codec_via_blosc_src.rs:113-128) writes c-blosc 1.x frames with
  * blosclz, lz4 / lz4hc, snappy, zlib or zstd streams after a byte shuffle / bitshuffle (frames any
  * c-blosc 1.x decoder reads, not byte-identical to c-blosc's).
  * enc_lens[n] receives each chunk's encoded length; descs[i].dst_cap must be >=
  * zgpu_chain_encoded_bound. zgpu_chain_encoded_bound: the fixed size, or the worst case
- * (gzip_codec.rs:122-136, zstd_codec.rs:132-147; a shard: every inner chunk at its bound + index),
+ * (gzip_codec.rs:122-136, zlib_codec.rs encoded_representation, zstd_codec.rs:132-147; a shard: every inner chunk at its bound + index),
  * -1 if unbounded.
  */
 int64_t zgpu_chain_encoded_bound(const zgpu_chain *chain, uint32_t ndim, const uint64_t *chunk_shape);

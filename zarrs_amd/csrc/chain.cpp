@@ -1,7 +1,8 @@
 // Codec chain parsing (see chain.hpp). Reference: codec_chain.rs:192-229 (from_metadata: exactly one
 // array->bytes codec, error otherwise), zarrs_codec/src/lib.rs:372-449 (name -> codec lookup), and the
 // per-codec configurations in zarrs_metadata_ext/src/codec/registered/{transpose,bytes,sharding,
-// crc32c,gzip,zstd,shuffle}.rs.
+// crc32c,gzip,zstd,shuffle}.rs, zarrs_metadata_ext/src/codec/numcodecs/{zlib,adler32,fletcher32}.rs
+// (created by zarrs/src/array/codec/bytes_to_bytes/{zlib,adler32,fletcher32}.rs).
 #include "chain.hpp"
 
 #include <cstring>
@@ -38,8 +39,7 @@ static bool zarrs_knows(const std::string &n) {
   static const char *names[] = {
       "bitround", "numcodecs.bitround", "cast_value", "numcodecs.fixedscaleoffset", "reshape", "zarrs.squeeze",
       "packbits", "numcodecs.pcodec", "zfp", "zarrs.zfp", "numcodecs.zfpy", "zarrs.vlen", "zarrs.vlen_v2",
-      "vlen-bytes", "vlen-utf8", "vlen-array", "zarrs.optional", "numcodecs.adler32", "numcodecs.bz2",
-      "numcodecs.fletcher32", "zarrs.gdeflate", "numcodecs.zlib"};
+      "vlen-bytes", "vlen-utf8", "vlen-array", "zarrs.optional", "numcodecs.bz2", "zarrs.gdeflate"};
   for (const char *k : names)
     if (n == k) return true;
   return n.rfind("https://codec.zarrs.dev/", 0) == 0;
@@ -108,6 +108,24 @@ static Role create_codec(Codec &k, const Json *cfg, const std::string &dt, uint3
     k.kind = CodecKind::Gzip;
     const Json *l = cfg_get("level");
     k.level = l ? (int)l->as_int() : 5;
+  } else if (k.name == "numcodecs.zlib") {
+    // ZlibCodecConfigurationV1 (zlib.rs:46-49): level 0..9, required
+    k.kind = CodecKind::Zlib;
+    const Json *l = cfg_get("level");
+    if (!l || l->kind != Json::Num || !l->is_int || l->i < 0 || l->i > 9)
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.zlib: level must be an integer 0..9"};
+    k.level = (int)l->i;
+  } else if (k.name == "numcodecs.adler32") {
+    // Adler32CodecConfigurationV1 (adler32.rs:47-59): location "start" (the default, unlike crc32c) / "end"
+    k.kind = CodecKind::Adler32;
+    k.at_start = true;
+    if (const Json *loc = cfg_get("location")) {
+      if (loc->kind == Json::Str && loc->s == "end") k.at_start = false;
+      else if (!(loc->kind == Json::Str && loc->s == "start"))
+        throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.adler32: location must be \"start\" or \"end\""};
+    }
+  } else if (k.name == "numcodecs.fletcher32" || k.name == "https://codec.zarrs.dev/bytes_to_bytes/fletcher32") {
+    k.kind = CodecKind::Fletcher32;  // no configuration (fletcher32.rs:47-49); the value sits at the end
   } else if (k.name == "zstd" || k.name == "numcodecs.zstd") {
     k.kind = CodecKind::Zstd;
     const Json *l = cfg_get("level");
@@ -219,13 +237,16 @@ int64_t chain_fixed_encoded_size(const Chain &c, uint64_t nelem) {
   if (c.a2b.kind != CodecKind::Bytes) return -1;
   int64_t n = (int64_t)(nelem * c.es);
   for (const Codec &k : c.b2b) {
-    if (k.kind == CodecKind::Crc32c) n += 4;
+    if (is_checksum(k.kind)) n += 4;
     else if (k.kind != CodecKind::Shuffle) return -1;
   }
   return n;
 }
 
 uint64_t gzip_bound(uint64_t n) { return n + 10 + 8 + (n + 7) / 8 + (n + 63) / 64 + 5; }
+
+// ZlibCodec::encoded_representation (zlib/zlib_codec.rs): zlib's compressBound
+uint64_t zlib_bound(uint64_t n) { return n + (n >> 12) + (n >> 14) + (n >> 25) + 13; }
 
 // ZstdCodec::encoded_representation (zstd_codec.rs:132-147): header/trailer 4 + 14 + 4 bytes and a
 // 3-byte block header per 1000 bytes
@@ -235,8 +256,9 @@ int64_t chain_encoded_bound(const Chain &c, uint64_t nelem) {
   if (c.a2b.kind != CodecKind::Bytes) return -1;
   uint64_t n = nelem * c.es;
   for (const Codec &k : c.b2b) {
-    if (k.kind == CodecKind::Crc32c) n += 4;
+    if (is_checksum(k.kind)) n += 4;
     else if (k.kind == CodecKind::Gzip) n = gzip_bound(n);
+    else if (k.kind == CodecKind::Zlib) n = zlib_bound(n);
     else if (k.kind == CodecKind::Zstd) n = zstd_bound(n);
     else if (k.kind == CodecKind::Blosc) n += 16;  // BLOSC_MAX_OVERHEAD (blosc_via_blosc_src.rs:80)
     else if (k.kind != CodecKind::Shuffle) return -1;

@@ -12,7 +12,7 @@
 
 namespace zgpu {
 
-enum class CodecKind { Transpose, Bytes, Sharding, Crc32c, Gzip, Zstd, Shuffle, Blosc };
+enum class CodecKind { Transpose, Bytes, Sharding, Crc32c, Gzip, Zstd, Shuffle, Blosc, Zlib, Adler32, Fletcher32 };
 
 struct Chain;
 
@@ -21,8 +21,8 @@ struct Codec {
   std::string name;
   std::vector<uint32_t> order;        // transpose
   bool big_endian = false;            // bytes
-  bool at_start = false;              // crc32c location / sharding index_location
-  int level = 0;                      // gzip / zstd
+  bool at_start = false;              // crc32c / adler32 location, sharding index_location
+  int level = 0;                      // gzip / zstd / zlib
   bool checksum = false;              // zstd
   uint32_t elementsize = 4;           // shuffle; blosc typesize
   std::string cname;                  // blosc compressor (decode reads the compressor from the header)
@@ -52,15 +52,22 @@ bool data_type_info(const std::string &name, uint32_t &es, uint32_t &comp);
 // Throws ChainError.
 std::shared_ptr<Chain> parse_chain(const Json &codecs, const std::string &data_type, const uint8_t *fill);
 
+// A 4-byte checksum codec (crc32c, numcodecs.adler32, numcodecs.fletcher32): fixed size + 4.
+inline bool is_checksum(CodecKind k) {
+  return k == CodecKind::Crc32c || k == CodecKind::Adler32 || k == CodecKind::Fletcher32;
+}
+
 // Encoded byte size of a chain for a fixed decoded element count, or -1 if not fixed-size
-// (BytesRepresentation::FixedSize, sharding.rs:163-176).
+// (BytesRepresentation::FixedSize, sharding.rs:163-176): the checksum codecs add 4 each.
 int64_t chain_fixed_encoded_size(const Chain &c, uint64_t nelem);
 
 // Upper bound of one chunk's encoded size for an array->bytes `bytes` chain (BytesRepresentation::
-// BoundedSize): crc32c +4, gzip as GzipCodec::encoded_representation (gzip_codec.rs:122-136, zlib's
-// deflateBound), zstd as ZstdCodec's (zstd_codec.rs:132-147); -1 if unbounded (e.g. blosc here).
+// BoundedSize): crc32c / adler32 / fletcher32 +4, gzip as GzipCodec::encoded_representation
+// (gzip_codec.rs:122-136, zlib's deflateBound), zlib as ZlibCodec's (zlib/zlib_codec.rs), zstd as
+// ZstdCodec's (zstd_codec.rs:132-147); -1 if unbounded.
 int64_t chain_encoded_bound(const Chain &c, uint64_t nelem);
 uint64_t gzip_bound(uint64_t n);
+uint64_t zlib_bound(uint64_t n);
 uint64_t zstd_bound(uint64_t n);
 
 }  // namespace zgpu

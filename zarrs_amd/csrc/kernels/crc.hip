@@ -11,9 +11,12 @@
 // Parallel CRC (crc.hpp): one workgroup per byte range, slice-by-4 segments merged by crc32_combine.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "../common.hpp"
 #include "crc.hpp"
 #include "launch.hpp"
+#include "linsum.hpp"
 
 namespace zgpu {
 
@@ -100,58 +103,200 @@ hipError_t launch_crc32c_strip(ZgItem *items, uint32_t *status, uint32_t n_items
 }
 
 // ------------------------------- Adler-32 (zlib trailer) ---------------------------------------
-// RFC 1950: s1 = 1 + sum b_j, s2 = sum of the running s1 = n + sum (n - j) b_j (mod 65521). Both sums
-// are linear in the bytes, so the threads take coalesced 4-byte words in any order (byte j adds b to A
-// and (n - j) b to B), reduce their residues every 4096 words, and the workgroup adds them.
-__global__ __launch_bounds__(CRC_THREADS) void k_adler32_check(const ZgItem *items, uint32_t *status,
-                                                               const uint32_t *kind, const uint2 *aux) {
-  constexpr uint32_t M = 65521;
-  __shared__ uint32_t s1s[CRC_THREADS], s2s[CRC_THREADS];
-  const uint32_t i = blockIdx.x, t = threadIdx.x;
+// The decoded stream's Adler-32 (linsum.hpp) against the trailer k_gzip<true> left in aux[i].x, for
+// the zlib streams of a blosc stream table (a plan's zlib stage checks it inside k_gzip).
+__global__ __launch_bounds__(CK_THREADS) void k_adler32_check(const ZgItem *items, uint32_t *status,
+                                                              const uint32_t *kind, const uint2 *aux) {
+  __shared__ uint32_t s_red[3 * CK_THREADS / 64];
+  const uint32_t i = blockIdx.x;
   if (kind[i] != BL_KIND_ZLIB || status[i] != 0) return;
   const ZgItem it = items[i];
-  const uint8_t *p = (const uint8_t *)it.src;
-  const uint64_t n = it.len;
-  uint64_t A = 0, B = 0;
-  uint32_t cnt = 0;
-  for (uint64_t j0 = 4ull * t; j0 < n; j0 += 4ull * CRC_THREADS) {
-    uint32_t w;
-    if (j0 + 4 <= n) {
-      __builtin_memcpy(&w, p + j0, 4);  // unaligned dword (gfx950 runs in unaligned mode)
-    } else {
-      w = 0;
-      for (uint32_t k = 0; j0 + k < n; k++) w |= (uint32_t)p[j0 + k] << (8 * k);
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {  // bytes past n are 0 and add nothing
-      const uint32_t b = (w >> (8 * k)) & 0xffu;
-      A += b;
-      B += (n - j0 - k) * b;  // blosc streams are < 2^31 bytes
-    }
-    if (++cnt == 4096) {  // B < 4096 * 4 * 2^32 * 255 < 2^56 between reductions
-      A %= M;
-      B %= M;
-      cnt = 0;
-    }
-  }
-  s1s[t] = (uint32_t)(A % M);
-  s2s[t] = (uint32_t)(B % M);
-  __syncthreads();
-  if (t == 0) {
-    uint64_t s1 = 1, s2 = n % M;
-    for (uint32_t k = 0; k < CRC_THREADS; k++) {
-      s1 += s1s[k];
-      s2 += s2s[k];
-    }
-    const uint32_t adler = (uint32_t)((s2 % M) << 16) | (uint32_t)(s1 % M);
-    if (adler != aux[i].x) status[i] = ZG_CORRUPT_STREAM;
-  }
+  const uint32_t adler = wg_checksum<CK_ADLER32>((const uint8_t *)it.src, it.len, s_red);
+  if (threadIdx.x == 0 && adler != aux[i].x) status[i] = ZG_CORRUPT_STREAM;
 }
 
 hipError_t launch_adler32_check(const ZgItem *subs, uint32_t *sub_status, const uint32_t *sub_kind, uint32_t n_sub,
                                 const uint2 *aux, hipStream_t s) {
   if (!n_sub) return hipSuccess;
-  hipLaunchKernelGGL(k_adler32_check, dim3(n_sub), dim3(CRC_THREADS), 0, s, subs, sub_status, sub_kind, aux);
+  hipLaunchKernelGGL(k_adler32_check, dim3(n_sub), dim3(CK_THREADS), 0, s, subs, sub_status, sub_kind, aux);
+  return hipGetLastError();
+}
+
+// ------------------------------- adler32 / fletcher32 stages ----------------------------------
+// numcodecs.adler32 (adler32_codec.rs: 4-byte LE value at Start (the default) or End) and
+// numcodecs.fletcher32 (fletcher32_codec.rs: 4-byte LE value at the end), with k_crc32c_strip's
+// semantics: an item below 4 bytes is CRC_INPUT_TOO_SHORT, verified only when the plan validates and
+// the item is not on the partial path, INVALID_CHECKSUM on a mismatch, then stripped.
+// Grid (items, Y): workgroup (i, y) sums ranges y, y + Y, ... of item i (linsum.hpp) into
+// parts[i * Y + y]; k_linsum_finish adds an item's Y parts, compares and strips. An item of at most
+// one range (and every item that is skipped or only stripped) is finished by its workgroup y = 0,
+// which says so in parts[i * Y].done. With Y = 1 the one workgroup of an item holds all its sums, so
+// it finishes the item whatever its length and there is no second launch. Y comes from the host's
+// guess at the items' lengths (an inner chunk's length is only known on the device): it decides how
+// many workgroups share an item, never the result.
+__device__ __forceinline__ uint32_t ck_le32(const uint8_t *p) {
+  return p[0] | p[1] << 8 | p[2] << 16 | (uint32_t)p[3] << 24;
+}
+
+template <uint32_t KIND>
+__global__ __launch_bounds__(CK_THREADS) void k_linsum_strip(ZgItem *items, uint32_t *status, CkPart *parts,
+                                                             int at_start, int verify) {
+  __shared__ uint32_t s_red[3 * CK_THREADS / 64];
+  const uint32_t i = blockIdx.x, y = blockIdx.y, Y = gridDim.y, t = threadIdx.x;
+  const ZgItem it = items[i];
+  CkPart *part = parts + (uint64_t)i * Y + y;
+  const bool lead = y == 0 && t == 0;
+  if (status[i] || (it.flags & ZG_ITEM_FILL)) {
+    if (lead) part->done = 1;
+    return;
+  }
+  if (it.len < 4) {
+    if (lead) {
+      status[i] = ZG_CRC_INPUT_TOO_SHORT;
+      part->done = 1;
+    }
+    return;
+  }
+  const uint8_t *base = (const uint8_t *)it.src;
+  const uint8_t *data = at_start ? base + 4 : base;
+  const uint8_t *stored = at_start ? base : base + it.len - 4;
+  const uint64_t len = it.len - 4, n = ck_covered<KIND>(len);
+  if (!verify || (it.flags & ZG_ITEM_PARTIAL)) {
+    if (lead) {
+      items[i].src = (uint64_t)data;
+      items[i].len = len;
+      part->done = 1;
+    }
+    return;
+  }
+  const bool alone = n <= CK_RANGE || Y == 1;  // this item's sums all belong to workgroup y = 0
+  if (alone && y) return;
+  CkSum acc{0, 0, 0};
+  for (uint64_t off = (uint64_t)y * CK_RANGE; off < n; off += (uint64_t)Y * CK_RANGE) {
+    const uint32_t m = (uint32_t)(n - off < CK_RANGE ? n - off : CK_RANGE);
+    const CkSum r = wg_linsum<KIND>(data + off, m, s_red);
+    ck_accumulate<KIND>(acc, r, n - off - m);
+  }
+  if (t) return;
+  if (!alone) {
+    *part = CkPart{acc.a, acc.b, acc.nz, 0};
+    return;
+  }
+  if (ck_value<KIND>(acc, len) != ck_le32(stored)) {
+    status[i] = ZG_INVALID_CHECKSUM;
+  } else {
+    items[i].src = (uint64_t)data;
+    items[i].len = len;
+  }
+  part->done = 1;
+}
+
+template <uint32_t KIND>
+__global__ void k_linsum_finish(ZgItem *items, uint32_t *status, const CkPart *parts, uint32_t n_items, uint32_t Y,
+                                int at_start) {
+  constexpr uint32_t M = ck_mod(KIND);
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_items) return;
+  const CkPart *part = parts + (uint64_t)i * Y;
+  if (part[0].done) return;
+  uint64_t a = 0, b = 0;  // Y <= CK_MAX_Y residues below 2^16
+  uint32_t nz = 0;
+  for (uint32_t y = 0; y < Y; y++) {
+    a += part[y].a;
+    b += part[y].b;
+    nz |= part[y].nz;
+  }
+  const ZgItem it = items[i];
+  const uint8_t *base = (const uint8_t *)it.src;
+  const uint8_t *data = at_start ? base + 4 : base;
+  const uint8_t *stored = at_start ? base : base + it.len - 4;
+  const CkSum sum{(uint32_t)(a % M), (uint32_t)(b % M), nz};
+  if (ck_value<KIND>(sum, it.len - 4) != ck_le32(stored)) {
+    status[i] = ZG_INVALID_CHECKSUM;
+    return;
+  }
+  items[i].src = (uint64_t)data;
+  items[i].len = it.len - 4;
+}
+
+uint32_t linsum_grid_y(uint64_t len_hint) {
+  const uint64_t y = (len_hint + CK_RANGE - 1) / CK_RANGE;
+  return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(y, 1), CK_MAX_Y);
+}
+
+uint64_t linsum_scratch_bytes(uint32_t n_items, uint64_t len_hint) {
+  return (uint64_t)n_items * linsum_grid_y(len_hint) * sizeof(CkPart);
+}
+
+template <uint32_t KIND>
+static hipError_t linsum_strip(ZgItem *items, uint32_t *status, uint32_t n_items, int at_start, int verify,
+                               uint64_t len_hint, void *scratch, hipStream_t s) {
+  const uint32_t Y = linsum_grid_y(len_hint);
+  // the y axis of a grid is limited to 65535 blocks, the x axis is not
+  hipLaunchKernelGGL(k_linsum_strip<KIND>, dim3(n_items, Y), dim3(CK_THREADS), 0, s, items, status, (CkPart *)scratch,
+                     at_start, verify);
+  if (Y > 1)
+    hipLaunchKernelGGL(k_linsum_finish<KIND>, dim3((n_items + 255) / 256), dim3(256), 0, s, items, status,
+                       (const CkPart *)scratch, n_items, Y, at_start);
+  return hipGetLastError();
+}
+
+hipError_t launch_linsum_strip(uint32_t kind, ZgItem *items, uint32_t *status, uint32_t n_items, int at_start,
+                               int verify, uint64_t len_hint, void *scratch, hipStream_t s) {
+  if (!n_items) return hipSuccess;
+  return kind == CK_ADLER32 ? linsum_strip<CK_ADLER32>(items, status, n_items, at_start, verify, len_hint, scratch, s)
+                            : linsum_strip<CK_FLETCHER32>(items, status, n_items, at_start, verify, len_hint, scratch, s);
+}
+
+// write path: the value of chunk c's bytes dsts[c] + [lo, lo + len), 4 bytes LE after or before them
+// (launch_crc32c_encode's pattern)
+template <uint32_t KIND>
+__global__ __launch_bounds__(CK_THREADS) void k_linsum_encode(const uint64_t *dsts, uint64_t lo, uint64_t len,
+                                                              int at_start) {
+  __shared__ uint32_t s_red[3 * CK_THREADS / 64];
+  if (!dsts[blockIdx.x]) return;
+  uint8_t *p = (uint8_t *)dsts[blockIdx.x] + lo;
+  const uint32_t c = wg_checksum<KIND>(p, len, s_red);
+  if (threadIdx.x == 0) {
+    uint8_t *w = at_start ? p - 4 : p + len;
+    for (int k = 0; k < 4; k++) w[k] = (uint8_t)(c >> (8 * k));
+  }
+}
+
+hipError_t launch_linsum_encode(uint32_t kind, const uint64_t *dsts, uint32_t n, uint64_t lo, uint64_t len,
+                                int at_start, hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (kind == CK_ADLER32)
+    hipLaunchKernelGGL(k_linsum_encode<CK_ADLER32>, dim3(n), dim3(CK_THREADS), 0, s, dsts, lo, len, at_start);
+  else
+    hipLaunchKernelGGL(k_linsum_encode<CK_FLETCHER32>, dim3(n), dim3(CK_THREADS), 0, s, dsts, lo, len, at_start);
+  return hipGetLastError();
+}
+
+// write path, items: every item's value written after its bytes (or before them: src moves back 4)
+template <uint32_t KIND>
+__global__ __launch_bounds__(CK_THREADS) void k_linsum_items(ZgItem *items, const uint32_t *status, int at_start) {
+  __shared__ uint32_t s_red[3 * CK_THREADS / 64];
+  const uint32_t i = blockIdx.x;
+  if (status[i]) return;
+  const ZgItem it = items[i];
+  uint8_t *p = (uint8_t *)it.src;
+  const uint32_t c = wg_checksum<KIND>(p, it.len, s_red);
+  if (threadIdx.x == 0) {
+    uint8_t *w = at_start ? p - 4 : p + it.len;
+    for (int k = 0; k < 4; k++) w[k] = (uint8_t)(c >> (8 * k));
+    items[i].src = at_start ? it.src - 4 : it.src;
+    items[i].len = it.len + 4;
+  }
+}
+
+hipError_t launch_linsum_items(uint32_t kind, ZgItem *items, const uint32_t *status, uint32_t n, int at_start,
+                               hipStream_t s) {
+  if (!n) return hipSuccess;
+  if (kind == CK_ADLER32)
+    hipLaunchKernelGGL(k_linsum_items<CK_ADLER32>, dim3(n), dim3(CK_THREADS), 0, s, items, status, at_start);
+  else
+    hipLaunchKernelGGL(k_linsum_items<CK_FLETCHER32>, dim3(n), dim3(CK_THREADS), 0, s, items, status, at_start);
   return hipGetLastError();
 }
 

@@ -372,9 +372,11 @@ __device__ uint32_t wave_adler32(const uint8_t *in, uint32_t n) {
 // u32 symbol records (one block's worth per wave). xfl: the header's XFL byte (flate2: 4 for level <= 1,
 // 2 for level >= 9, else 0). zhdr != 0: a zlib stream (RFC 1950) instead, CMF FLG = zhdr, at slot i +
 // GZE_HDR + 8 (the same bit stream position), with the Adler-32 trailer (blosc's zlib streams).
+// zbounded (with zhdr): a stream longer than zlib's compressBound of its input, or than the slot, is
+// written again as 65,535-byte stored blocks (n + 5 per block + 6 bytes: within the bound for every n).
 __global__ __launch_bounds__(64) void k_gzip_encode(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *slots,
                                                     uint64_t slot_bytes, uint32_t *sym_scratch, uint32_t xfl,
-                                                    uint32_t zhdr) {
+                                                    uint32_t zhdr, uint32_t zbounded) {
   __shared__ GzeSmem S;
   const uint32_t lane = threadIdx.x;
   uint32_t *syms = sym_scratch + (uint64_t)blockIdx.x * GZE_BLK_SYMS;
@@ -505,8 +507,19 @@ __global__ __launch_bounds__(64) void k_gzip_encode(ZgItem *items, uint32_t *sta
       put(S, B, crc, 32);
       put(S, B, n, 32);
     }
-    const uint64_t total_bits = (uint64_t)B.outw * 32 + B.bitpos;
+    uint64_t total_bits = (uint64_t)B.outw * 32 + B.bitpos;
     flush(S, B, true);
+    if (zhdr && zbounded) {
+      const uint64_t n64 = n, bound = n64 + (n64 >> 12) + (n64 >> 14) + (n64 >> 25) + 13;
+      if (B.ovf || 2 + total_bits / 8 > bound) {  // flush(all) left S.bits clear
+        B = BitOut{0, 0, (uint32_t *)(slot + GZE_HDR + 10), (uint32_t)((slot_bytes - GZE_HDR - 10) / 4), 0};
+        emit_stored(S, B, in, 0, n, true);
+        maybe_flush(S, B);
+        put(S, B, __builtin_bswap32(crc), 32);
+        total_bits = (uint64_t)B.outw * 32 + B.bitpos;
+        flush(S, B, true);
+      }
+    }
     if (lane == 0) {
       if (B.ovf) {
         status[item] = ZG_DECODED_SIZE_MISMATCH;
@@ -524,7 +537,7 @@ uint32_t gzip_encode_grid(uint32_t n_items) {
 }
 
 hipError_t launch_gzip_encode(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *slots, uint64_t slot_bytes,
-                              uint32_t *sym_scratch, int level, hipStream_t s, bool zlib) {
+                              uint32_t *sym_scratch, int level, hipStream_t s, bool zlib, bool zlib_bounded) {
   if (!n_items) return hipSuccess;
   const uint32_t xfl = level <= 1 ? 4u : level >= 9 ? 2u : 0u;
   uint32_t zhdr = 0;
@@ -534,7 +547,7 @@ hipError_t launch_gzip_encode(ZgItem *items, uint32_t *status, uint32_t n_items,
     zhdr |= (31u - zhdr % 31u) % 31u;
   }
   hipLaunchKernelGGL(k_gzip_encode, dim3(gzip_encode_grid(n_items)), dim3(64), 0, s, items, status, n_items, slots,
-                     slot_bytes, sym_scratch, xfl, zhdr);
+                     slot_bytes, sym_scratch, xfl, zhdr, zlib_bounded ? 1u : 0u);
   return hipGetLastError();
 }
 

@@ -39,6 +39,7 @@
 #include "../common.hpp"
 #include "crc.hpp"
 #include "launch.hpp"
+#include "linsum.hpp"
 
 namespace zgpu {
 
@@ -1152,12 +1153,16 @@ __device__ __forceinline__ bool exec_batch(SM &S, const OutMap &O, uint64_t cap,
 // (gzip_codec.rs:110-120: flate2's GzDecoder fails on a mismatch); aux is unused.
 // zlib (ZLIB = true, RFC 1950; blosc's zlib streams, c-blosc zlib_wrap_decompress = zlib uncompress):
 // only items whose kind is BL_KIND_ZLIB and status BL_SKIP; aux[i] = {Adler-32, 0}, status 0 on
-// success (the Adler-32 check follows in k_adler32_check).
-template <bool ZLIB, bool PIPE = false>
+// success (the Adler-32 check follows in k_adler32_check). PLAN: the items of a plan's numcodecs.zlib
+// stage (zlib_codec.rs) instead, selected by status 0 like gzip's; the Adler-32 of the slot is checked
+// here, as gzip's CRC-32 is (flate2's ZlibDecoder checks it whatever validate_checksums says), and
+// kind / aux are unused.
+template <bool ZLIB, bool PIPE = false, bool PLAN = false>
 __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu(PIPE ? 4 : ZG_INFLATE_WPE, 8))) void k_gzip(
     ZgItem *items, uint32_t *status, const uint32_t *kind, uint8_t *dst, uint64_t slot_bytes, uint2 *aux,
     const uint32_t *order, uint32_t *seg_scr, int crc_tail, GzDirect gd) {
   static_assert(!(ZLIB && PIPE), "the pipelined mode is for gzip streams");
+  static_assert(ZLIB || !PLAN, "PLAN selects the zlib kernel's items");
   __shared__ std::conditional_t<PIPE, SmemP, Smem> S;
 #if !ZG_INFLATE_XFETCH
   __shared__ uint16_t seg_base[65], seg_skip[64];
@@ -1165,7 +1170,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
   PROF_DECL;
   PROF_T(t_all);
   const uint32_t item = order ? order[blockIdx.x] : blockIdx.x;
-  if (ZLIB ? (kind[item] != BL_KIND_ZLIB || status[item] != BL_SKIP) : status[item] != 0) return;
+  if (ZLIB && !PLAN ? (kind[item] != BL_KIND_ZLIB || status[item] != BL_SKIP) : status[item] != 0) return;
   const ZgItem it = items[item];
   if (it.flags & ZG_ITEM_FILL) return;
   const int lane = lane_id();
@@ -1916,7 +1921,17 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
     if (ZLIB) {  // trailer: Adler-32, big endian
       const uint32_t b0 = bits_get(B, 8), b1 = bits_get(B, 8), b2 = bits_get(B, 8), b3 = bits_get(B, 8);
       if (B.consumed > end_bits) err = ZG_CORRUPT_STREAM;
-      if (lane == 0 && !err) aux[item] = make_uint2((b0 << 24) | (b1 << 16) | (b2 << 8) | b3, 0u);
+      const uint32_t trailer = (b0 << 24) | (b1 << 16) | (b2 << 8) | b3;
+      if constexpr (PLAN) {
+        if (!err) {  // the whole stream is in the slot, flushed by this wave (as for the CRC-32 below)
+          __threadfence_block();
+          wsync();
+          const uint32_t a = wg_checksum<CK_ADLER32, 64>(out, pos, nullptr);
+          if (__shfl(a, 0, 64) != trailer) err = ZG_CORRUPT_STREAM;
+        }
+      } else if (lane == 0 && !err) {
+        aux[item] = make_uint2(trailer, 0u);
+      }
     } else {  // trailer: CRC-32 then ISIZE (little endian), checked against the decoded stream
       const uint32_t crc_lo = bits_get(B, 16);
       const uint32_t crc_hi = bits_get(B, 16);
@@ -1949,7 +1964,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
     } else {
       items[item].src = (uint64_t)out;
       items[item].len = pos;
-      if (ZLIB) status[item] = 0;
+      if (ZLIB && !PLAN) status[item] = 0;
       if (O.cfg >> 31) {  // in the array already: the scatter skips it (its size check is made here)
         if (pos != O.want) status[item] = ZG_DECODED_SIZE_MISMATCH;
         else items[item].flags = it.flags | ZG_ITEM_DIRECT;
@@ -2018,17 +2033,23 @@ uint64_t gzip_seg_scratch_bytes(uint32_t n_items) {
   return on ? slots * 64 * SEGCAP * 4 : 0;
 }
 
-hipError_t launch_gzip(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst, uint64_t slot_bytes,
-                       uint32_t *order, uint32_t *seg_scr, hipStream_t s, int crc_tail, const GzDirect *direct,
-                       const GzCrcFork *crc_fork) {
-  const GzDirect gd = direct ? *direct : GzDirect{};
-  if (!n_items) return hipSuccess;
+// What every launch of k_gzip over a plan's items (gzip or zlib) decides first: the LPT order
+// (ZGPU_GZIP_LPT=0 or a lone item: none) and whether the segmented decode's scratch is used.
+static void gzip_launch_knobs(uint32_t n_items, uint32_t *&order, uint32_t *&seg_scr) {
   static const bool lpt = [] {
     const char *e = std::getenv("ZGPU_GZIP_LPT");
     return !e || std::atoi(e) != 0;
   }();
   if (!lpt || n_items < 2) order = nullptr;
   if (!gzip_seg_scratch_bytes(1)) seg_scr = nullptr;
+}
+
+hipError_t launch_gzip(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst, uint64_t slot_bytes,
+                       uint32_t *order, uint32_t *seg_scr, hipStream_t s, int crc_tail, const GzDirect *direct,
+                       const GzCrcFork *crc_fork) {
+  const GzDirect gd = direct ? *direct : GzDirect{};
+  if (!n_items) return hipSuccess;
+  gzip_launch_knobs(n_items, order, seg_scr);
   const bool pipe = seg_scr && n_items <= gzip_pipe_max();  // few streams: the pipelined latency mode
   // a trailing crc32c: checked inside the pipelined kernel (its second wave is idle at the start), by
   // k_crc32c_strip ahead of the one-wave kernel (inside it the check cost more HBM traffic: r05cal)
@@ -2070,6 +2091,16 @@ hipError_t launch_gzip(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_
     if (e == hipSuccess) e = launch_crc32c_merge(status, crc_fork->bad, n_items, s);
     if (e != hipSuccess) return e;
   }
+  return hipGetLastError();
+}
+
+hipError_t launch_zlib_items(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst, uint64_t slot_bytes,
+                             uint32_t *order, uint32_t *seg_scr, hipStream_t s) {
+  if (!n_items) return hipSuccess;
+  gzip_launch_knobs(n_items, order, seg_scr);
+  if (order) hipLaunchKernelGGL(k_order_by_len, dim3(1), dim3(1024), 0, s, items, status, n_items, order);
+  hipLaunchKernelGGL((k_gzip<true, false, true>), dim3(n_items), dim3(64), 0, s, items, status, nullptr, dst,
+                     slot_bytes, nullptr, order, seg_scr, 0, GzDirect{});
   return hipGetLastError();
 }
 

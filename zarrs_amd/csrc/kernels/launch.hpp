@@ -58,6 +58,15 @@ hipError_t launch_box_copy(const uint8_t *src, uint8_t *dst, const ZgBoxCopy &P,
 hipError_t launch_crc32c_strip(ZgItem *items, uint32_t *status, uint32_t n_items, int at_start, int verify,
                                hipStream_t s);
 
+// numcodecs.adler32 / numcodecs.fletcher32 (kind: CK_ADLER32 / CK_FLETCHER32, kernels/linsum.hpp):
+// verify + strip of the 4-byte LE value with launch_crc32c_strip's semantics. len_hint: the host's
+// guess of the longest item (it sizes the grid's workgroups per item, not the result); scratch:
+// linsum_scratch_bytes(n_items, len_hint) bytes.
+enum : uint32_t { CK_ADLER32 = 0, CK_FLETCHER32 = 1 };
+uint64_t linsum_scratch_bytes(uint32_t n_items, uint64_t len_hint);
+hipError_t launch_linsum_strip(uint32_t kind, ZgItem *items, uint32_t *status, uint32_t n_items, int at_start,
+                               int verify, uint64_t len_hint, void *scratch, hipStream_t s);
+
 // Shard index: decode every shard's index (bytes{endian} + optional crc32c chain), then resolve
 // each sharded item's {src,len} or fill flag.  index_crc: 0 none, 1 end, 2 start.
 struct ZgIndexSpec {
@@ -191,6 +200,9 @@ hipError_t launch_encode_gather(const uint64_t *dsts, const uint64_t *starts, co
                                 const ZgEncode &P, uint32_t n_chunks, hipStream_t s);
 hipError_t launch_crc32c_encode(const uint64_t *dsts, uint32_t n, uint64_t lo, uint64_t len, int at_start,
                                 hipStream_t s);
+// the same for an adler32 / fletcher32 codec (kind: CK_ADLER32 / CK_FLETCHER32)
+hipError_t launch_linsum_encode(uint32_t kind, const uint64_t *dsts, uint32_t n, uint64_t lo, uint64_t len,
+                                int at_start, hipStream_t s);
 // sharding_indexed encode of fixed-size inner chains: fill check of every inner chunk (geometry of
 // `inner`, origins `starts`), C-order layout + raw index per shard, copy of the encoded inner chunks
 // (temporary slots of E_pitch bytes) into the shards. The index crc32c codecs run afterwards
@@ -208,12 +220,16 @@ hipError_t launch_shard_encode(const uint64_t *starts, const uint8_t *array, con
 // gzip member encode (deflate_enc.hip): item i's bytes -> a member written at slot i + GZE_HDR (the
 // headroom takes crc32c codecs located at the start), items rewritten to it. sym_scratch holds
 // gzip_encode_grid(n) * GZE_BLK_SYMS u32 symbol records. zlib: a zlib stream (RFC 1950, Adler-32
-// trailer) at slot i + GZE_HDR + 8 instead of a gzip member (blosc's zlib streams).
+// trailer) at slot i + GZE_HDR + 8 instead of a gzip member (blosc's zlib streams). zlib_bounded (the
+// numcodecs.zlib codec): a stream that would pass zlib's compressBound (ZlibCodec's encoded bound;
+// the encoder's blocks are shorter than zlib's, so incompressible input of several MiB can) is
+// written again as stored blocks of 65,535 bytes, which always fit it.
 constexpr uint32_t GZE_BLK_SYMS = 16384;  // symbols per DEFLATE block
 constexpr uint64_t GZE_HDR = 62;          // member offset in a slot (its bit stream then starts word-aligned)
 uint32_t gzip_encode_grid(uint32_t n_items);
 hipError_t launch_gzip_encode(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *slots, uint64_t slot_bytes,
-                              uint32_t *sym_scratch, int level, hipStream_t s, bool zlib = false);
+                              uint32_t *sym_scratch, int level, hipStream_t s, bool zlib = false,
+                              bool zlib_bounded = false);
 // zstd frame encode (zstd_enc.hip): item i's bytes (at most max_len) -> one single-segment frame at
 // slot i + ZE_HDR, items rewritten to it; the work is cut into 1 MiB segments, one wave each.
 // scratch: zstd_encode_scratch(n_items, max_len) bytes
@@ -223,6 +239,9 @@ hipError_t launch_zstd_encode(ZgItem *items, uint32_t *status, uint32_t n_items,
                               uint64_t slot_bytes, uint8_t *scratch, int checksum, hipStream_t s);
 // crc32c of each item's bytes written after them (or before them with at_start: src moves back 4)
 hipError_t launch_crc32c_items(ZgItem *items, const uint32_t *status, uint32_t n, int at_start, hipStream_t s);
+// the same for an adler32 / fletcher32 codec
+hipError_t launch_linsum_items(uint32_t kind, ZgItem *items, const uint32_t *status, uint32_t n, int at_start,
+                               hipStream_t s);
 // each item's bytes into dst[i] (capacity cap[i], else DECODED_SIZE_MISMATCH); lens[i] = length
 hipError_t launch_encode_place(const ZgItem *items, uint32_t *status, const uint64_t *dst, const uint64_t *cap,
                                uint64_t *lens, uint32_t n, hipStream_t s);
@@ -301,6 +320,12 @@ hipError_t launch_zlib_streams(ZgItem *subs, uint32_t *sub_status, const uint32_
                                uint8_t *dst, uint64_t slot, uint2 *aux, uint32_t *seg_scr, hipStream_t s);
 hipError_t launch_adler32_check(const ZgItem *subs, uint32_t *sub_status, const uint32_t *sub_kind, uint32_t n_sub,
                                 const uint2 *aux, hipStream_t s);
+// numcodecs.zlib stage of a plan (zlib_codec.rs; flate2's ZlibDecoder): every live item inflated into
+// its dst slot by the one-wave k_gzip<true> (order / seg_scr as for launch_gzip), which also checks the
+// Adler-32 trailer over the slot, whatever the plan validates (a mismatch is CORRUPT_STREAM); bytes
+// after the stream are ignored.
+hipError_t launch_zlib_items(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst, uint64_t slot_bytes,
+                             uint32_t *order, uint32_t *seg_scr, hipStream_t s);
 hipError_t launch_blosc_layout(const BlInfo *info, uint32_t n_items, uint64_t *bases, const BlCaps &caps,
                                const BlDecode &D, hipStream_t s);
 hipError_t launch_blosc_info(const ZgItem *items, uint32_t *status, uint32_t n_items, uint64_t slot_bytes,

@@ -297,7 +297,12 @@ struct zgpu_chain {
 // ------------------------------------------------------------------------------------------------
 // Plan
 // ------------------------------------------------------------------------------------------------
-enum StageKind { ST_CRC32C, ST_GZIP, ST_ZSTD, ST_UNSHUFFLE, ST_BLOSC };
+enum StageKind { ST_CRC32C, ST_GZIP, ST_ZSTD, ST_UNSHUFFLE, ST_BLOSC, ST_ADLER32, ST_FLETCHER32, ST_ZLIB };
+// the checksum stages strip 4 bytes in place; every other stage materialises its output in a slot pool
+static bool strips_only(StageKind k) { return k == ST_CRC32C || k == ST_ADLER32 || k == ST_FLETCHER32; }
+static StageKind checksum_stage(CodecKind k) {
+  return k == CodecKind::Crc32c ? ST_CRC32C : k == CodecKind::Adler32 ? ST_ADLER32 : ST_FLETCHER32;
+}
 struct Stage {
   StageKind kind;
   int at_start = 0;
@@ -390,7 +395,10 @@ struct zgpu_plan {
     size_t n = 0;
   };
   Grow bl_info, bl_bases, bl_subs, bl_sub_status, bl_sub_kind, bl_blocks, bl_tmp, bl_zblks, bl_znblk, bl_zmode,
-      bl_zlit, bl_zseq, bl_zaux, bl_zser, bl_lzl, bl_zseg, bl_zrec, bl_zalias, bl_znorm, gz_crc, live_list;
+      bl_zlit, bl_zseq, bl_zaux, bl_zser, bl_lzl, bl_zseg, bl_zrec, bl_zalias, bl_znorm, gz_crc, live_list,
+      ck_parts;  // ck_parts: the adler32 / fletcher32 stages' range sums
+  uint64_t in_len_hint = 0;  // the longest item before any stage, as far as the host knows: how many
+                             // workgroups a checksum stage gives an item (k_linsum_strip), not its result
   uint8_t *bl_h = nullptr;  // pinned: BlInfo read-back (first execution)
   size_t bl_h_n = 0;
   void *grow(Grow &g, size_t bytes) {
@@ -458,7 +466,7 @@ struct zgpu_plan {
       if (e) (void)hipEventDestroy(e);
     for (Grow *g : {&bl_info, &bl_bases, &bl_subs, &bl_sub_status, &bl_sub_kind, &bl_blocks, &bl_tmp, &bl_zblks,
                     &bl_znblk, &bl_zmode, &bl_zlit, &bl_zseq, &bl_zaux, &bl_zser, &bl_lzl, &bl_zseg, &bl_zrec, &bl_zalias,
-                    &bl_znorm, &gz_crc, &live_list})
+                    &bl_znorm, &gz_crc, &live_list, &ck_parts})
       ctx->dev_free(g->p);
     ctx->host_free(bl_h);
     ctx->host_free(h_ctl);
@@ -518,8 +526,8 @@ static void build_leaf_stages(zgpu_plan &P, const Chain &leaf, uint64_t nelem) {
   for (int i = nb - 1; i >= 0; i--) {
     const Codec &k = leaf.b2b[i];
     Stage s;
-    if (k.kind == CodecKind::Crc32c) {
-      s.kind = ST_CRC32C;
+    if (is_checksum(k.kind)) {
+      s.kind = checksum_stage(k.kind);
       s.at_start = k.at_start;
       P.stages.push_back(s);
       continue;
@@ -531,12 +539,13 @@ static void build_leaf_stages(zgpu_plan &P, const Chain &leaf, uint64_t nelem) {
     // materialising stage: its output is the encoded representation of codecs [bytes, b2b_0..i-1]
     int64_t out_size = (int64_t)(nelem * leaf.es);
     for (int j = 0; j < i; j++) {
-      if (leaf.b2b[j].kind == CodecKind::Crc32c) out_size += 4;
+      if (is_checksum(leaf.b2b[j].kind)) out_size += 4;
       else if (leaf.b2b[j].kind != CodecKind::Shuffle) out_size = -1;
       if (out_size < 0) break;
     }
     if (out_size < 0) throw ChainError{ZGPU_UNSUPPORTED, "a compressor nested inside another variable-size codec"};
     s.kind = k.kind == CodecKind::Gzip    ? ST_GZIP
+             : k.kind == CodecKind::Zlib  ? ST_ZLIB
              : k.kind == CodecKind::Zstd  ? ST_ZSTD
              : k.kind == CodecKind::Blosc ? ST_BLOSC
                                           : ST_UNSHUFFLE;
@@ -933,7 +942,7 @@ static void plan_upload(zgpu_plan &P, hipStream_t us) {
       HIPCHK(hipMemcpyAsync(P.d_bl_need, P.bl_need.data(), P.bl_need.size() * 8, hipMemcpyHostToDevice, us));
     }
     for (const Stage &s : P.stages) {
-      if (s.kind == ST_GZIP && !P.d_order) {
+      if ((s.kind == ST_GZIP || s.kind == ST_ZLIB) && !P.d_order) {
         P.d_order = (uint32_t *)C.dev_alloc(ni * 4);
         if (const uint64_t b = gzip_seg_scratch_bytes((uint32_t)ni)) P.d_gz_seg = (uint32_t *)C.dev_alloc(b);
       }
@@ -961,6 +970,22 @@ static void plan_upload(zgpu_plan &P, hipStream_t us) {
       }
     }
   }
+  // the longest encoded item: known for plain chunks; an inner chunk's length comes from its shard's
+  // index on the device, so the chain's bound stands in for it (no more than the longest shard)
+  P.in_len_hint = 0;
+  if (P.sharded) {
+    uint64_t shard_max = 0;
+    for (const ZgShard &sh : P.shards) shard_max = std::max(shard_max, sh.len);
+    const int64_t b = P.leaf ? chain_encoded_bound(*P.leaf, P.scatter.nelem) : -1;
+    P.in_len_hint = b >= 0 ? std::min<uint64_t>((uint64_t)b, shard_max) : shard_max;
+  } else {
+    for (const ZgItem &it : P.items) P.in_len_hint = std::max(P.in_len_hint, it.len);
+  }
+  // one scratch for every checksum stage of the plan, sized for the longest input any of them can be
+  // given a hint of (the stages run one after another on the plan's stream)
+  for (const Stage &s : P.stages)
+    if (ni && (s.kind == ST_ADLER32 || s.kind == ST_FLETCHER32))
+      P.grow(P.ck_parts, linsum_scratch_bytes((uint32_t)ni, std::max(P.in_len_hint, P.slot_bytes)));
   P.ctl_bytes = 256 + ni * 4;
   P.d_ctl = (uint8_t *)C.dev_alloc(P.ctl_bytes);
   P.h_ctl = (uint8_t *)C.host_alloc(P.ctl_bytes);
@@ -1129,9 +1154,20 @@ static void plan_enqueue(zgpu_plan &P, uint8_t *out, hipStream_t s) {
   }
   int crc_tail = 0;  // a trailing crc32c stage handed to the next gzip stage (launch_gzip places it)
   bool wrote_direct = false;  // a stage wrote whole items into the output (the scatter lists the rest)
+  uint64_t len_hint = P.in_len_hint;  // of the current stage's input (a slot after a materialising stage)
   for (size_t si = 0; si < P.stages.size(); si++) {
     const Stage &st = P.stages[si];
     switch (st.kind) {
+      case ST_ADLER32:
+      case ST_FLETCHER32: {
+        HIPCHK(launch_linsum_strip(st.kind == ST_ADLER32 ? CK_ADLER32 : CK_FLETCHER32, P.d_items, P.d_status, ni,
+                                   st.at_start, P.validate ? 1 : 0, len_hint, P.ck_parts.p, s));  // sized in plan_upload
+        break;
+      }
+      case ST_ZLIB:
+        HIPCHK(launch_zlib_items(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.slot_bytes, P.d_order, P.d_gz_seg,
+                                 s));
+        break;
       case ST_CRC32C:
         if (!st.at_start && si + 1 < P.stages.size() && P.stages[si + 1].kind == ST_GZIP && P.d_gz_seg) {
           crc_tail = P.validate ? 1 : 2;
@@ -1183,6 +1219,7 @@ static void plan_enqueue(zgpu_plan &P, uint8_t *out, hipStream_t s) {
         HIPCHK(launch_unshuffle(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.slot_bytes, st.elementsize, s));
         break;
     }
+    if (!strips_only(st.kind)) len_hint = P.slot_bytes;
   }
   if (!P.no_scatter) {
     // A/B (ZGPU_SCATTER_LIST=1): after the gzip direct rows, the rows scatter over a device-built list
@@ -1210,7 +1247,7 @@ static void size_detail(zgpu_plan &P, uint64_t d, const uint32_t *st, hipStream_
     HIPCHK(hipStreamSynchronize(s));
     bool materialised = false, exact = true;
     for (const Stage &stg : P.stages)
-      if (stg.kind != ST_CRC32C) materialised = true;
+      if (!strips_only(stg.kind)) materialised = true;
     if (materialised) {
       exact = false;
       for (int k = 0; k < P.n_pools; k++) {
@@ -1415,7 +1452,8 @@ static void run_sub(GeneralCall &G, const std::shared_ptr<Chain> &chain, const s
 // One bytes->bytes codec applied to whole shards (items[i] = shard i's current bytes; ist[i] its
 // status): decoded by a stages-only plan whose slots hold the decoded shards. Compressors size the
 // slots from the streams (kernels/probe.hip); a gzip member longer than its ISIZE hint is re-run
-// with larger slots up to DEFLATE's 1032:1 bound.
+// with larger slots up to DEFLATE's 1032:1 bound, and so is a zlib stream, which carries no size:
+// its slots start at four times the encoded shard.
 static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &items, std::vector<int32_t> &ist) {
   std::vector<uint32_t> todo;
   for (uint32_t i = 0; i < items.size(); i++)
@@ -1424,8 +1462,11 @@ static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &ite
   Stage st{};
   uint32_t hint_kind = UINT32_MAX;
   switch (k.kind) {
-    case CodecKind::Crc32c: st.kind = ST_CRC32C; st.at_start = k.at_start; break;
+    case CodecKind::Crc32c:
+    case CodecKind::Adler32:
+    case CodecKind::Fletcher32: st.kind = checksum_stage(k.kind); st.at_start = k.at_start; break;
     case CodecKind::Gzip: st.kind = ST_GZIP; hint_kind = SIZE_HINT_GZIP; break;
+    case CodecKind::Zlib: st.kind = ST_ZLIB; break;  // no size in the stream: the regrow loop below finds it
     case CodecKind::Zstd: st.kind = ST_ZSTD; hint_kind = SIZE_HINT_ZSTD; break;
     case CodecKind::Blosc: st.kind = ST_BLOSC; hint_kind = SIZE_HINT_BLOSC; break;
     case CodecKind::Shuffle: st.kind = ST_UNSHUFFLE; st.elementsize = k.elementsize; break;
@@ -1434,6 +1475,8 @@ static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &ite
   uint64_t cap = 0;
   if (st.kind == ST_UNSHUFFLE) {
     for (uint32_t t : todo) cap = std::max(cap, items[t].len);
+  } else if (st.kind == ST_ZLIB) {
+    for (uint32_t t : todo) cap = std::max(cap, items[t].len * 4);  // a first guess; regrown 8x on a mismatch
   } else if (hint_kind != UINT32_MAX) {
     const uint32_t nt = (uint32_t)todo.size();
     std::vector<ZgItem> hi(nt);
@@ -1471,7 +1514,7 @@ static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &ite
     }
     st.pool = 0;
     P->stages = {st};
-    P->n_pools = st.kind == ST_CRC32C ? 0 : 1;
+    P->n_pools = strips_only(st.kind) ? 0 : 1;
     P->slot_bytes = (c + 255) & ~(uint64_t)255;
     P->no_scatter = true;
     plan_upload(*P, G.s);
@@ -1508,7 +1551,7 @@ static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &ite
   for (size_t j = 0; j < todo.size(); j++) {
     const uint32_t t = todo[j];
     const uint64_t bound = std::min(items[t].len * 1032 + 1024, slot_limit);
-    if (s[j] == ZGPU_DECODED_SIZE_MISMATCH && st.kind == ST_GZIP && cap < bound)
+    if (s[j] == ZGPU_DECODED_SIZE_MISMATCH && (st.kind == ST_GZIP || st.kind == ST_ZLIB) && cap < bound)
       again.push_back(t);
     else
       settle(t, s[j], res[j]);
@@ -3170,9 +3213,10 @@ static int encode_fixed(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t
   for (size_t i = 0; i < c.b2b.size(); i++) {
     const Codec &k = c.b2b[i];
     if (k.kind == CodecKind::Shuffle && i == 0 && k.elementsize == c.es) shuffle = true;
-    else if (k.kind == CodecKind::Crc32c) n_start += k.at_start ? 1 : 0;
+    else if (is_checksum(k.kind)) n_start += k.at_start ? 1 : 0;
     else return set_err(ZGPU_UNSUPPORTED, "encode: only transpose / bytes / numcodecs.shuffle (innermost, "
-                                          "elementsize = data type size) / crc32c / gzip run on the GPU write path");
+                                          "elementsize = data type size) / crc32c / adler32 / fletcher32 / gzip run "
+                                          "on the GPU write path");
   }
   ZgEncode P = encode_params(c, nd, chunk_shape, array_shape, shuffle, 4ull * n_start);
   bool aligned = (P.data_off % c.es) == 0;
@@ -3187,8 +3231,12 @@ static int encode_fixed(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t
   HIPCHK(launch_encode_gather(d, d + n, (const uint8_t *)array, P, (uint32_t)n, s));
   uint64_t lo = P.data_off, len = P.nelem * c.es;
   for (const Codec &k : c.b2b) {
-    if (k.kind != CodecKind::Crc32c) continue;
-    HIPCHK(launch_crc32c_encode(d, (uint32_t)n, lo, len, k.at_start ? 1 : 0, s));
+    if (!is_checksum(k.kind)) continue;
+    if (k.kind == CodecKind::Crc32c)
+      HIPCHK(launch_crc32c_encode(d, (uint32_t)n, lo, len, k.at_start ? 1 : 0, s));
+    else
+      HIPCHK(launch_linsum_encode(k.kind == CodecKind::Adler32 ? CK_ADLER32 : CK_FLETCHER32, d, (uint32_t)n, lo, len,
+                                  k.at_start ? 1 : 0, s));
     if (k.at_start) lo -= 4;
     len += 4;
   }
@@ -3197,7 +3245,9 @@ static int encode_fixed(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t
 
 static bool chain_compresses(const Chain &c) {
   for (const Codec &k : c.b2b)
-    if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zstd || k.kind == CodecKind::Blosc) return true;
+    if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib || k.kind == CodecKind::Zstd ||
+        k.kind == CodecKind::Blosc)
+      return true;
   return false;  // (blosc is refused by encode_var: its encoder is not on the GPU)
 }
 
@@ -3223,27 +3273,31 @@ static int encode_var(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t *
     const Codec &k = c.b2b[i];
     if (k.kind == CodecKind::Shuffle && i == 0 && k.elementsize == c.es) {
       shuffle = true;
-    } else if (k.kind == CodecKind::Crc32c) {
+    } else if (is_checksum(k.kind)) {
       size += 4;
       n_crc++;
     } else if (k.kind == CodecKind::Gzip) {
       size = gzip_bound(size);
+    } else if (k.kind == CodecKind::Zlib) {
+      size = zlib_bound(size);  // k_gzip_encode keeps to it (zlib_bounded)
     } else if (k.kind == CodecKind::Zstd) {
       size = zstd_bound(size);
     } else if (k.kind == CodecKind::Blosc) {
       size += 16;
     } else {
       return set_err(ZGPU_UNSUPPORTED, "encode: only transpose / bytes / numcodecs.shuffle (innermost, elementsize = "
-                                       "data type size) / crc32c / gzip / zstd / blosc run on the GPU write path");
+                                       "data type size) / crc32c / adler32 / fletcher32 / gzip / zlib / zstd / blosc "
+                                       "run on the GPU write path");
     }
     max_size = std::max(max_size, size);
   }
-  if (n_crc > 14) return set_err(ZGPU_UNSUPPORTED, "encode: too many crc32c codecs");
+  if (n_crc > 14) return set_err(ZGPU_UNSUPPORTED, "encode: too many checksum codecs");
   constexpr uint64_t HR = 64;  // headroom in front of a slot's bytes (crc32c at the start)
   const uint64_t pitch = (HR + max_size + 4 * n_crc + 16 + 255) & ~(uint64_t)255;
   bool gz = false;  // a compressor: its output goes to the other slot pool
   for (const Codec &k : c.b2b)
-    gz = gz || k.kind == CodecKind::Gzip || k.kind == CodecKind::Zstd || k.kind == CodecKind::Blosc;
+    gz = gz || k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib || k.kind == CodecKind::Zstd ||
+         k.kind == CodecKind::Blosc;
   uint8_t *pool[2] = {(uint8_t *)C->dev_alloc(std::max<uint64_t>(n * pitch, 1)), nullptr};
   owned.push_back(pool[0]);
   if (gz) {
@@ -3301,18 +3355,23 @@ static int encode_var(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t *
       var_len = true;
       continue;
     }
-    if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zstd) var_len = true;
-    in_size = k.kind == CodecKind::Crc32c ? in_size + 4 : k.kind == CodecKind::Gzip ? gzip_bound(in_size)
+    if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib || k.kind == CodecKind::Zstd) var_len = true;
+    in_size = is_checksum(k.kind) ? in_size + 4 : k.kind == CodecKind::Gzip ? gzip_bound(in_size)
+              : k.kind == CodecKind::Zlib ? zlib_bound(in_size)
               : k.kind == CodecKind::Zstd ? zstd_bound(in_size) : in_size;
     if (k.kind == CodecKind::Crc32c) {
       HIPCHK(launch_crc32c_items(d_items, d_status, (uint32_t)n, k.at_start ? 1 : 0, s));
-    } else if (k.kind == CodecKind::Gzip) {
+    } else if (k.kind == CodecKind::Adler32 || k.kind == CodecKind::Fletcher32) {
+      HIPCHK(launch_linsum_items(k.kind == CodecKind::Adler32 ? CK_ADLER32 : CK_FLETCHER32, d_items, d_status,
+                                 (uint32_t)n, k.at_start ? 1 : 0, s));
+    } else if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib) {
       if (!sym) {
         sym = (uint32_t *)C->dev_alloc((uint64_t)gzip_encode_grid((uint32_t)std::max<uint64_t>(n, 1)) * GZE_BLK_SYMS * 4);
         owned.push_back(sym);
       }
       cur ^= 1;
-      HIPCHK(launch_gzip_encode(d_items, d_status, (uint32_t)n, pool[cur], pitch, sym, k.level, s));
+      HIPCHK(launch_gzip_encode(d_items, d_status, (uint32_t)n, pool[cur], pitch, sym, k.level, s,
+                                k.kind == CodecKind::Zlib, k.kind == CodecKind::Zlib));
     } else if (k.kind == CodecKind::Zstd) {
       zscr = (uint8_t *)C->dev_alloc(zstd_encode_scratch((uint32_t)n, stage_in));
       owned.push_back(zscr);
