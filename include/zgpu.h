@@ -308,7 +308,9 @@ void zgpu_group_destroy(zgpu_group *group);
                                     covering the bytes it reads (blosc_partial_decoder.rs:33-60)     */
 #define ZGPU_CTR_ITEMS 5         /* leaf items the call planned: chunks, or inner chunks of shards that meet
                                     the selection (each decoded, or filled when empty)                 */
-#define ZGPU_N_COUNTERS 6
+#define ZGPU_CTR_ZSTD_LATENCY 6  /* zstd items finished by the window executor's latency mode (a subset
+                                    of ZGPU_CTR_ZSTD_PARALLEL: small batches, one workgroup per window) */
+#define ZGPU_N_COUNTERS 7
 uint32_t zgpu_plan_counters(const zgpu_plan *plan, uint64_t *out, uint32_t n);
 uint32_t zgpu_last_counters(uint64_t *out, uint32_t n);
 

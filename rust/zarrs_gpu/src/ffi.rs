@@ -52,7 +52,9 @@ pub struct zgpu_group {
 
 /// zgpu_last_counters index: leaf items (chunks / inner chunks) the calling thread's last call planned.
 pub const ZGPU_CTR_ITEMS: usize = 5;
-pub const ZGPU_N_COUNTERS: usize = 6;
+/// zgpu_last_counters index: zstd items finished by the window executor's latency mode.
+pub const ZGPU_CTR_ZSTD_LATENCY: usize = 6;
+pub const ZGPU_N_COUNTERS: usize = 7;
 
 /// zgpu_encode_desc: one chunk of a device-resident array encoded into `dst`.
 #[repr(C)]

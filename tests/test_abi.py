@@ -37,6 +37,21 @@ def test_desc_struct_layout_matches_header():
     assert L.ChunkDesc.chunk_shape.offset == 16
 
 
+def test_counter_indices_match_header():
+    """The ctypes mirror's counter indices, their number and last_counters()' keys follow zgpu.h."""
+    from zarrs_amd import _lib as L
+    txt = open(HEADER).read()
+    defs = {k: int(v) for k, v in re.findall(r"#define ZGPU_CTR_(\w+) (\d+)", txt)}
+    n = int(re.search(r"#define ZGPU_N_COUNTERS (\d+)", txt).group(1))
+    assert sorted(defs.values()) == list(range(n)) and L.N_COUNTERS == n
+    for name, idx in defs.items():
+        assert getattr(L, "CTR_" + name) == idx, name
+    assert defs["ZSTD_LATENCY"] == 6
+    ctr = L.last_counters()  # no decode call yet on this thread: every counter reads 0
+    assert {"enc_bytes", "zstd_serial", "zstd_parallel", "blosc_rerun", "blosc_blocks", "zstd_latency"} <= set(ctr)
+    assert all(v == 0 for v in ctr.values())
+
+
 def test_status_names_and_version():
     from zarrs_amd import _lib as L
     lib = L.load()

@@ -247,8 +247,7 @@ int main(int argc, char **argv) {
       hipLaunchKernelGGL(zgpu::k_zstd_exec_win<true>, dim3(ncu), dim3(zgpu::xwin::THREADS), 0, 0, d_items, d_status,
                          blks, Z.blk_cap, Z.nblk, Z.mode, d_out, chunk, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap,
                          (uint32_t)n, Z.ext, (const unsigned long long *)nullptr);
-      uint32_t rounds = 2;
-      while (rounds < zgpu::ZEXT_ROUNDS && (1ull << (rounds - 2)) < chunk / 1024 + 1) rounds++;
+      const uint32_t rounds = zgpu::zstd_ext_rounds(Z.blk_cap, chunk);
       const uint32_t g2 = (uint32_t)std::min<uint64_t>((tot / 4 + 255) / 256, (uint64_t)ncu * 16);
       uint32_t *ea = Z.ext, *eb = Z.ext + tot;
       for (uint32_t r = 0; r < rounds; r++) {
@@ -257,7 +256,8 @@ int main(int argc, char **argv) {
         std::swap(ea, eb);
       }
       hipLaunchKernelGGL(zgpu::k_zstd_par_finish, dim3(n), dim3(64), 0, 0, d_items, d_status, blks, Z.blk_cap, Z.nblk,
-                         Z.mode, d_out, chunk);
+                         Z.mode, d_out, chunk, (const uint32_t *)ea, (const unsigned long long *)(Z.ext_cnt + rounds - 1),
+                         (unsigned long long *)nullptr);
     } else if (xk == 2)
       hipLaunchKernelGGL(zgpu::k_zstd_exec_win<false>, dim3(n * xseg), dim3(zgpu::xwin::THREADS), 0, 0, d_items,
                          d_status, blks, Z.blk_cap, Z.nblk, Z.mode, d_out, chunk, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap,

@@ -46,8 +46,9 @@ EXPORTS = [
     "zgpu_group_create", "zgpu_group_execute", "zgpu_group_status", "zgpu_group_layout",
     "zgpu_group_algorithmic_bytes", "zgpu_group_counters", "zgpu_group_destroy",
 ]
-CTR_ENC_BYTES, CTR_ZSTD_SERIAL, CTR_ZSTD_PARALLEL, CTR_BLOSC_RERUN, CTR_BLOSC_BLOCKS, CTR_ITEMS = range(6)
-N_COUNTERS = 6
+CTR_ENC_BYTES, CTR_ZSTD_SERIAL, CTR_ZSTD_PARALLEL, CTR_BLOSC_RERUN, CTR_BLOSC_BLOCKS, CTR_ITEMS, \
+    CTR_ZSTD_LATENCY = range(7)
+N_COUNTERS = 7
 
 
 class ChunkDesc(C.Structure):
@@ -206,7 +207,7 @@ def last_counters() -> dict:
     buf = (C.c_uint64 * N_COUNTERS)()
     load().zgpu_last_counters(buf, N_COUNTERS)
     return {"enc_bytes": buf[0], "zstd_serial": buf[1], "zstd_parallel": buf[2], "blosc_rerun": buf[3],
-            "blosc_blocks": buf[4]}
+            "blosc_blocks": buf[4], "zstd_latency": buf[6]}
 
 
 def last_size_mismatch():

@@ -161,11 +161,14 @@ struct ZstdScratch {
   uint32_t *ext = nullptr;
   unsigned long long *ext_cnt = nullptr;
   uint64_t ext_items = 0;
+  unsigned long long *lat_count = nullptr;  // items the latency mode finished (nullable)
 };
 constexpr uint32_t ZALIAS = 2;
 // latency mode: batches of at most this many decoded bytes (n_items x slot) get the ext arrays
 constexpr uint64_t ZPAR_MAX_BYTES = 128ull << 20;
 constexpr uint32_t ZEXT_ROUNDS = 24;
+// rounds of k_zstd_ext_round for items of blk_cap block records and slot_bytes decoded bytes
+uint32_t zstd_ext_rounds(uint32_t blk_cap, uint64_t slot_bytes);
 constexpr uint64_t ZALIAS_RLE = 1ull << 63;
 uint64_t zstd_lit_rec_bytes(uint32_t &wgs);
 // bytes of FSE-count scratch per block record (ZstdScratch::norm)

@@ -4428,6 +4428,27 @@ void zstd_scratch_layout(uint64_t slot_bytes, uint32_t &blk_cap, uint64_t &blk_b
   lit_stride = (lit_stride + 255) & ~(uint64_t)255;
   seq_cap = slot_bytes / 4 + 1024;  // sequences per item (each decodes >= 3 bytes; typical >= 8)
 }
+// Latency mode: the pointer-jumping rounds k_zstd_ext_round is launched for (tools/lab/zstd_lab.cpp runs
+// the same rule).
+// Every hop of a reference chain leaves its window for an earlier window of the item (a
+// cell is external only when its source lies before its window's start, exec_task), so a chain has
+// at most as many hops as the item has windows. A latency-mode window ends at (a) its block's end:
+// at most blk_cap of these; (b) the end of its workgroup's WSPAN range of the block: at most
+// slot / WSPAN; (c) the end of a full sequence table (T = 1024 sequences of >= 3 bytes each): such
+// a window starts either where the previous table ended, and then spans >= 3 T bytes (at most
+// slot / (3 T) of these), or at its workgroup's range start (at most one per range: slot / WSPAN
+// again). The W-cell limit never ends one: W > WSPAN. So
+//   hops <= blk_cap + 2 slot / WSPAN + slot / (3 T) + 1,
+// and pointer jumping resolves a chain of d hops in floor(log2 d) + 1 rounds (each round halves
+// it); ceil(log2 hops) + 1 rounds are launched, at most ZEXT_ROUNDS (the largest latency batch,
+// ZPAR_MAX_BYTES in one item, needs 17). A round after the last reference returns at once, and
+// k_zstd_par_finish reads the last round's count: an item with a reference left reports an error.
+uint32_t zstd_ext_rounds(uint32_t blk_cap, uint64_t slot_bytes) {
+  const uint64_t hops = (uint64_t)blk_cap + 2 * (slot_bytes / xwin::WSPAN) + slot_bytes / (3 * xwin::T) + 1;
+  uint32_t rounds = 1;
+  while (rounds < ZEXT_ROUNDS && (1ull << (rounds - 1)) < hops) rounds++;
+  return rounds;
+}
 // One pass of the block-parallel pipeline over n_items items on stream s; ev_entropy (nullable) is
 // recorded on s once the entropy kernels (and the side stream's sequence decode) are done.
 static hipError_t launch_zstd_pass(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst,
@@ -4575,11 +4596,8 @@ static hipError_t launch_zstd_pass(ZgItem *items, uint32_t *status, uint32_t n_i
     hipLaunchKernelGGL(k_zstd_exec_win<true>, dim3(device_cu_count()), dim3(xwin::THREADS), 0, s, items, status,
                        blks, Z.blk_cap, Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap,
                        n_items, Z.ext, Z.max_nblk);
-    // rounds: a reference hops back at least one window range (or one table's sub-window, >= 1 KiB on
-    // real data) per step, so log2 of the slot's KiB + 2 rounds; a round after the last reference
-    // returns at once
-    uint32_t rounds = 2;
-    while (rounds < ZEXT_ROUNDS && (1ull << (rounds - 2)) < slot_bytes / 1024 + 1) rounds++;
+    // rounds: from the bound on an item's windows (zstd_ext_rounds above)
+    const uint32_t rounds = zstd_ext_rounds(Z.blk_cap, slot_bytes);
     const uint32_t g2 = (uint32_t)std::min<uint64_t>((tot / 4 + 255) / 256, (uint64_t)device_cu_count() * 16);
     uint32_t *ea = Z.ext, *eb = Z.ext + tot;
     for (uint32_t r = 0; r < rounds; r++) {
@@ -4588,7 +4606,8 @@ static hipError_t launch_zstd_pass(ZgItem *items, uint32_t *status, uint32_t n_i
       std::swap(ea, eb);
     }
     hipLaunchKernelGGL(k_zstd_par_finish, dim3(n_items), dim3(64), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
-                       dst, slot_bytes);
+                       dst, slot_bytes, (const uint32_t *)ea, (const unsigned long long *)(Z.ext_cnt + rounds - 1),
+                       Z.lat_count);
   } else if (xwin_on)
     hipLaunchKernelGGL(k_zstd_exec_win<false>, dim3(n_items * xseg), dim3(xwin::THREADS), 0, s, items, status, blks,
                        Z.blk_cap, Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, xseg,

@@ -27,8 +27,10 @@
 // every window of every block gets a workgroup of its own, all at once. A cell whose chain leaves its
 // window is not loaded (the byte may not exist yet) but becomes an external reference (32-bit cells:
 // EXT | item position); k_zstd_ext_round then resolves the external references by pointer jumping
-// over the whole output (ping-pong arrays, one launch per round: a chain crosses at most one window per
-// hop, so log2(windows) + 1 rounds), and k_zstd_par_finish checks frame checksums.
+// over the whole output (ping-pong arrays, one launch per round: every hop of a chain leaves a window
+// for an earlier one, so ceil(log2(an item's windows)) + 1 rounds; the bound on the windows is at the
+// zstd_ext_rounds in zstd.hip), and k_zstd_par_finish checks that no reference is left and the frame
+// checksums.
 // Reference behaviour: zarrs/src/array/codec/bytes_to_bytes/zstd/zstd_codec.rs:113-130 (libzstd
 // ZSTD_decompress; RFC 8878 3.1.1.4 sequence execution).
 namespace xwin {
@@ -521,16 +523,33 @@ __global__ __launch_bounds__(256) void k_zstd_ext_round(const uint32_t *ea, uint
 }
 
 // Latency mode, last step: frame checksums over the resolved output and the items' decoded records
-// (one wave per item).
+// (one wave per item). ext_fin / cnt_last: the ext array and the reference count the last round left;
+// an item with a reference still in it (only when the count is not 0) is an error, never status 0
+// over unresolved bytes. With zstd_ext_rounds' bound no legal frame leaves a reference, so no test
+// reaches that branch: it is a guard for a bound that a later change breaks. lat_count (nullable): the
+// items finished here.
 __global__ __launch_bounds__(64) void k_zstd_par_finish(ZgItem *items, uint32_t *status, const ZBlk *blks,
                                                         uint32_t blk_cap, const uint32_t *nblk,
-                                                        const uint32_t *zmode, uint8_t *dst, uint64_t slot_bytes) {
+                                                        const uint32_t *zmode, uint8_t *dst, uint64_t slot_bytes,
+                                                        const uint32_t *ext_fin,
+                                                        const unsigned long long *cnt_last,
+                                                        unsigned long long *lat_count) {
   const uint32_t item = blockIdx.x;
   const int lane = lane_id();
   if (zmode[item] != ZMODE_PARALLEL || status[item]) return;
   uint8_t *out = dst + (uint64_t)item * slot_bytes;
   const ZBlk *B = blks + (uint64_t)item * blk_cap;
   const uint32_t nb = nblk[item];
+  if (*cnt_last) {  // some item of the batch has references left: is it this one?
+    const uint32_t *e = ext_fin + (uint64_t)item * slot_bytes;
+    const uint64_t end = nb ? min<uint64_t>((uint64_t)U(B[nb - 1].out_off) + U(B[nb - 1].out_size), slot_bytes) : 0;
+    bool left = false;
+    for (uint64_t p = lane; p < end && !left; p += 64) left = e[p] != xwin::EXT_NONE;
+    if (__ballot(left)) {
+      if (lane == 0) status[item] = ZG_CORRUPT_STREAM;
+      return;
+    }
+  }
   for (uint32_t base = 0; base < nb; base += 64) {
     uint64_t m = __ballot(base + lane < nb && (B[base + lane].flags & (ZBF_LAST | ZBF_CK)) == (ZBF_LAST | ZBF_CK));
     while (m) {
@@ -547,5 +566,6 @@ __global__ __launch_bounds__(64) void k_zstd_par_finish(ZgItem *items, uint32_t 
   if (lane == 0) {
     items[item].src = (uint64_t)out;
     items[item].len = nb ? (uint64_t)B[nb - 1].out_off + B[nb - 1].out_size : 0;
+    if (lat_count) atomicAdd(lat_count, 1ull);
   }
 }

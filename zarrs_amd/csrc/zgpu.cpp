@@ -40,7 +40,7 @@ namespace {
 thread_local std::string g_last_error;
 // device counters in the plan's control block (u64 each, cleared per execute)
 enum { CTR_ENC_BYTES = 0, CTR_ZSTD_SERIAL = 1, CTR_ZSTD_PARALLEL = 2, CTR_BLOSC_RERUN = 3, CTR_BLOSC_BLOCKS = 4,
-       CTR_ITEMS = 5, CTR_N = 6 };  // CTR_ITEMS is host-side (the plan's leaf items)
+       CTR_ITEMS = 5, CTR_ZSTD_LATENCY = 6, CTR_N = 7 };  // CTR_ITEMS is host-side (the plan's leaf items)
 // internal ctl slots (not reported): a cached blosc layout was outgrown (the execution is re-run)
 enum { CTR_BLOSC_OVF = 31, CTR_SCRATCH = 30, CTR_ZSTD_NSER = 29, CTR_ZSTD_MAXBLK = 28 };  // not reported (device-side flags / sinks)
 thread_local uint64_t g_last_counters[CTR_N];
@@ -992,6 +992,7 @@ static void plan_upload(zgpu_plan &P, hipStream_t us) {
   P.d_counter = (unsigned long long *)P.d_ctl;
   P.d_status = (uint32_t *)(P.d_ctl + 256);
   P.zs.counters = P.d_counter + CTR_ZSTD_SERIAL;
+  P.zs.lat_count = P.d_counter + CTR_ZSTD_LATENCY;
   P.zs.ser_count = P.d_counter + CTR_ZSTD_NSER;
   P.zs.max_nblk = P.d_counter + CTR_ZSTD_MAXBLK;
   if (const char *e = std::getenv("ZGPU_ZSTD_FORCE_SERIAL")) P.zs.force_serial = std::atoi(e) != 0;
