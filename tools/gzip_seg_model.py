@@ -9,7 +9,14 @@ first 64 bit positions start a symbol on its chain. Lane l is right when lane l-
 lane l's records before the exit are dropped. The first wrong lane is re-decoded from its
 predecessor's exit (at most MAXREP times a round); the round ends at the last right lane.
 
-Test infrastructure (tests/test_gzip_seg_model.py), not the product path.
+inflate_stream() also keeps the batch executor's accounting (ExecAcct: batches, pending bytes, where
+each match's source lies relative to the ring and the flushed output), each block's table shapes under
+build_table's allocation rule (table_shape) and each dynamic header's lane-parallel decode windows
+(header_windows): what tests/deflate_streams.py's cases state their intent over. KERNEL holds the
+kernel's segment constants (inflate_seg's defaults are older values its own test relies on).
+
+Test infrastructure (tests/test_gzip_seg_model.py, tests/test_deflate_streams_model.py), not the
+product path.
 """
 from __future__ import annotations
 
@@ -107,7 +114,13 @@ def seg_decode(B, p, s_own, s_end, end_bits, lt, dt, cap):
     return END, p, recs, mask
 
 
-def decode_block_seg(B, r0, end_bits, lt, dt, segb, ovl, cap, maxrep, stats):
+def _eob_start(lane, lt):
+    """Start bit of the end-of-block code a lane stopped at (its exit is the bit after it)."""
+    ln = next(ln for (ln, _), s in lt[0].items() if s == 256)
+    return lane["p"] - ln
+
+
+def decode_block_seg(B, r0, end_bits, lt, dt, segb, ovl, cap, maxrep, stats, rounds_out=None):
     """Records of one Huffman block from r0 and the bit after its end-of-block code."""
     out = []
     while True:
@@ -130,6 +143,8 @@ def decode_block_seg(B, r0, end_bits, lt, dt, segb, ovl, cap, maxrep, stats):
             if j == 64:
                 break
             if lanes[j - 1]["st"] != END or rep >= maxrep:
+                if lanes[j - 1]["st"] == END:
+                    stats["maxrep_cuts"] = stats.get("maxrep_cuts", 0) + 1  # the round cut by MAXREP
                 for l in range(j, 64):
                     lanes[l]["ok"] = False
                 break
@@ -140,10 +155,21 @@ def decode_block_seg(B, r0, end_bits, lt, dt, segb, ovl, cap, maxrep, stats):
         J = next((l for l in range(64) if not lanes[l]["ok"]), 64)
         stats["rounds"] += 1
         stats["valid_lanes"] += J
+        rnd = []
         for l in range(J):
-            out.extend(lanes[l]["recs"][lanes[l]["skip"]:])
+            rnd.extend(lanes[l]["recs"][lanes[l]["skip"]:])
+        out.extend(rnd)
+        if rounds_out is not None:
+            rounds_out.append(rnd)
         last = lanes[J - 1]
+        if last["st"] == CAP:
+            stats["cap_hits"] = stats.get("cap_hits", 0) + 1  # a lane region filled its SEGCAP records
         if last["st"] == EOB:
+            # where the end-of-block code started: in the region of lane J-1 (off bits past its s_own;
+            # to_end bits before its region's end, inside the next lane's overlap when <= ovl)
+            q = _eob_start(last, lt)
+            stats.setdefault("eob", []).append(dict(lane=J - 1, off=q - last["s_own"], repaired=last["rep"],
+                                                    to_end=last["s_own"] + segb - q))
             return out, last["p"]
         if last["st"] in (END, CAP):
             r0 = last["p"]
@@ -165,8 +191,109 @@ def inflate_seg(gz: bytes, segb=512, ovl=256, cap=64, maxrep=8, stats=None):
             hp = gz.index(b"\0", hp) + 1
     if flg & 2:
         hp += 2
+    return inflate_stream(gz, hp, 8, segb, ovl, cap, maxrep, stats)
+
+
+# The kernel's constants (kernels/inflate.hip): the segment decode's and the batch executor's.
+KERNEL = dict(segb=512, ovl=384, cap=96, maxrep=8)
+RING, BATCH_CAP, FLUSH_MIN, BATCH_SYMS = 1024, 480, 256, 64
+# BATCH_CAP was RING / 2: up to RING bytes were then unflushed in a batch (B + f), and from RING - 30 on
+# the executor read stale bytes (tests/deflate_streams.py's executor_ring family reaches that state
+# under this value and must not under the kernel's)
+BATCH_CAP_RING_HALF = 512
+
+
+def table_shape(lens, root):
+    """(longest code, second-level table entries) of a code set under the kernel's allocation rule
+    (build_table): every root prefix of codes longer than the root gets 2^(its longest code - root)."""
+    t, mx = table(lens)
+    sub = {}
+    for (ln, rc), _ in t.items():
+        if ln > root:
+            c = int(format(rc, "0%db" % ln)[::-1], 2)  # MSB-first code
+            pre = c >> (ln - root)
+            sub[pre] = max(sub.get(pre, 0), ln - root)
+    return mx, sum(1 << b for b in sub.values())
+
+
+def header_windows(syms, total):
+    """The lane-parallel header decode's windows over a dynamic header's code-length symbols
+    [(symbol, bits, lengths it writes)]: a window takes the symbols that start within its first 63
+    bits, at most 32 of them, up to the header's last length. Per window: `take` (the symbols taken),
+    `starts` (symbol starts within its 63 bits), `first` (index of its first length) and `last_end`
+    (the window bit at which its last taken symbol ends: past 63 when that symbol reaches out of it)."""
+    wins, i, n = [], 0, 0
+    while n < total and i < len(syms):
+        off, take, starts, j, first, last_end = 0, [], 0, i, n, 0
+        while j < len(syms) and off < 63:
+            starts += 1
+            if len(take) < 32 and n < total:
+                take.append(syms[j][0])
+                n += syms[j][2]
+                i = j + 1
+                last_end = off + syms[j][1]
+            off += syms[j][1]
+            j += 1
+        wins.append(dict(take=take, starts=starts, first=first, last_end=last_end))
+    return wins
+
+
+class ExecAcct:
+    """The batch executor's accounting (exec_batch and its callers): a round's records go in batches of
+    at most BATCH_SYMS symbols, taken while the batch holds fewer than batch_cap bytes; the ring is
+    flushed once FLUSH_MIN bytes are pending; a stored block flushes everything. Per batch: B (its
+    bytes), f (bytes pending at its start), and for each match where its source lies: the source start
+    in the ring or older (`start_in_ring`: what the kernel's per-match test sees), and its last source
+    byte flushed or not (`last_flushed`)."""
+
+    def __init__(self, batch_cap=BATCH_CAP):
+        self.pos = self.flushed = 0
+        self.batches = []
+        self.batch_cap = batch_cap
+
+    def stored(self, n):
+        self.pos += n
+        self.flushed = self.pos
+
+    def round(self, recs):
+        g = 0
+        while g < len(recs):
+            b, k = 0, g
+            while k < len(recs) and k - g < BATCH_SYMS and b < self.batch_cap:
+                b += (recs[k] & 511) if recs[k] >> 31 else 1
+                k += 1
+            end, q, ms = self.pos + b, self.pos, []
+            for r in recs[g:k]:
+                if r >> 31:
+                    dist, ln = (r >> 9) & 0xFFFF, r & 511
+                    src = q - dist
+                    ms.append(dict(len=ln, dist=dist, src=src, start_in_ring=src + RING >= end,
+                                   last_flushed=src + min(ln, dist) - 1 < self.flushed,
+                                   last=src + min(ln, dist) - 1))
+                    q += ln
+                else:
+                    q += 1
+            self.batches.append(dict(B=b, f=self.pos - self.flushed, pos=self.pos, flushed=self.flushed,
+                                     syms=k - g, matches=ms))
+            self.pos = end
+            if self.pos - self.flushed >= FLUSH_MIN:
+                self.flushed = self.pos
+            g = k
+
+
+def inflate_stream(data: bytes, start: int, trailer: int, segb=512, ovl=256, cap=64, maxrep=8, stats=None,
+                   batch_cap=BATCH_CAP):
+    """The DEFLATE stream at byte `start` of `data` (`trailer` bytes follow it) -> decoded bytes through
+    the segmented decode, with the executor's accounting in stats["batches"], each Huffman block's
+    table shapes in stats["tables"] and each dynamic header's windows in stats["hdr"]."""
+    stats = stats if stats is not None else {}
+    for k in ("rounds", "valid_lanes", "repairs", "blocks", "maxrep_cuts", "cap_hits"):
+        stats.setdefault(k, 0)
+    acct = ExecAcct(batch_cap)
+    stats["batches"] = acct.batches
+    gz, hp = data, start
     B = Bits(gz)
-    end_bits = (len(gz) - 8) * 8
+    end_bits = (len(gz) - trailer) * 8
     p, out, last = hp * 8, bytearray(), False
     while not last:
         last, typ = B.get(p, 1), B.get(p + 1, 2)
@@ -178,6 +305,7 @@ def inflate_seg(gz: bytes, segb=512, ovl=256, cap=64, maxrep=8, stats=None):
             p += 32
             out += gz[p // 8:p // 8 + n]
             p += 8 * n
+            acct.stored(n)
             continue
         if typ == 1:
             lens = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8
@@ -190,23 +318,36 @@ def inflate_seg(gz: bytes, segb=512, ovl=256, cap=64, maxrep=8, stats=None):
                 cl[CLEN_ORDER[i]] = B.get(p, 3)
                 p += 3
             ct = table(cl)
-            ll = []
+            ll, syms = [], []
             while len(ll) < hlit + hdist:
                 s, n = read_sym(B, p, *ct)
                 p += n
+                k = len(ll)
                 if s < 16:
                     ll.append(s)
                 elif s == 16:
                     ll += [ll[-1]] * (3 + B.get(p, 2))
                     p += 2
+                    n += 2
                 elif s == 17:
                     ll += [0] * (3 + B.get(p, 3))
                     p += 3
+                    n += 3
                 else:
                     ll += [0] * (11 + B.get(p, 7))
                     p += 7
+                    n += 7
+                syms.append((s, n, len(ll) - k))
+            assert len(ll) == hlit + hdist, "a run past the header's last length"
+            stats.setdefault("hdr", []).append(dict(hlit=hlit, hdist=hdist, hclen=hclen, syms=syms, clmax=ct[1],
+                                                    windows=header_windows(syms, hlit + hdist)))
             lens, dl = ll[:hlit], ll[hlit:]
-        recs, p = decode_block_seg(B, p, end_bits, table(lens), table(dl), segb, ovl, cap, maxrep, stats)
+        stats.setdefault("tables", []).append(dict(zip(("lmax", "lsub", "dmax", "dsub"),
+                                                       table_shape(lens, 9) + table_shape(dl, 8))))
+        rounds = []
+        recs, p = decode_block_seg(B, p, end_bits, table(lens), table(dl), segb, ovl, cap, maxrep, stats, rounds)
+        for rnd in rounds:
+            acct.round(rnd)
         for r in recs:  # LZ77
             if r >> 31:
                 dist, ln = (r >> 9) & 0xFFFF, r & 511

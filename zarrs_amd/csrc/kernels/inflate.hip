@@ -66,13 +66,13 @@ namespace {
 #define ZG_INFLATE_RING 1024
 #endif
 // LDS ring of recent output (power of two). Small on purpose: sources older than the ring are read
-// back from the flushed output (L2-resident), and a 1 KiB ring (512-B batches, 256-B flushes)
+// back from the flushed output (L2-resident), and a 1 KiB ring (512-B batches then, 256-B flushes)
 // measured faster than 2 KiB (42.5 -> 39.5 ms) and 512 B (40.5 ms) on C3 chunks at the same 5 waves
 // per SIMD (profiles/r02_gzip_lab_ring_ab.txt).
 constexpr int RING = ZG_INFLATE_RING;
 constexpr int RMASK = RING - 1;
 #ifndef ZG_INFLATE_BATCH_CAP
-#define ZG_INFLATE_BATCH_CAP (RING / 2)
+#define ZG_INFLATE_BATCH_CAP (RING / 2 - 32)
 #endif
 #ifndef ZG_INFLATE_FLUSH_MIN
 #define ZG_INFLATE_FLUSH_MIN (RING / 4)
@@ -83,6 +83,13 @@ constexpr int FLUSH_MIN = ZG_INFLATE_FLUSH_MIN;  // flush the ring to the slot o
 // symbols while it holds fewer than BATCH_CAP bytes, the last one a match of at most 258. So every
 // source older than the ring has been flushed, and no unflushed byte is overwritten.
 static_assert((FLUSH_MIN - 1) + (BATCH_CAP - 1) + 258 <= RING, "gzip ring: unflushed bytes must fit it");
+// They also stay 31 bytes short of it. exec_batch's per-lane copy (matches of at most 32 bytes) decides
+// ring or flushed output once, from the source's first byte: with RING - 30 or more bytes unflushed a
+// source could start older than the ring and end in bytes not flushed yet, and was then read stale
+// from the slot (a valid stream failed its own CRC; with BATCH_CAP = RING / 2 up to RING bytes were
+// unflushed). And flush()'s first 16-B piece starts up to 15 bytes before `flushed`: with more than
+// RING - 15 bytes unflushed those bytes' ring slots hold newer output, which it wrote over them.
+static_assert((FLUSH_MIN - 1) + (BATCH_CAP - 1) + 258 <= RING - 31, "gzip ring: a short match's source is in the ring or flushed, whole");
 #ifndef ZG_INFLATE_LROOT
 #define ZG_INFLATE_LROOT 9
 #endif
