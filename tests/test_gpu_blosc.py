@@ -10,6 +10,7 @@ import pytest
 
 import fixtures as F
 import oracle as O
+from blosc_frames import _blosc_snappy_frame, _snappy_compress, varint as _varint  # noqa: F401  (test_snappy_writer.py reads _snappy_compress here)
 
 pytestmark = pytest.mark.gpu
 
@@ -304,100 +305,9 @@ def test_blosc_plan_cached_layout_and_rerun(ctx, torch_cuda, cname):
 # (raw format, google/snappy format_description.txt) that emits every element form — inline and
 # 1-4-byte literal lengths, copies with 1-, 2- and 4-byte offsets, overlapping copies — inside c-blosc
 # 1.x frames (16-B header, bstarts, {csize, stream} per split; a stream whose compressed size would
-# reach the split's size is stored). Parity unpinned (no snappy library in the image): checked by
-# round trip against the encoded data.
-def _varint(v):
-    out = bytearray()
-    while True:
-        b = v & 127
-        v >>= 7
-        out.append(b | (128 if v else 0))
-        if not v:
-            return bytes(out)
-
-
-def _snappy_literal(out, lit, rng):
-    while lit:
-        n = len(lit) if len(lit) <= 200 else int(rng.integers(1, len(lit) + 1))
-        if n <= 60 and rng.random() < 0.7:
-            out.append((n - 1) << 2)
-        else:  # 60..63: the length - 1 in 1..4 little-endian bytes (any width that holds it is valid)
-            nb = max(1, ((n - 1).bit_length() + 7) // 8)
-            nb = min(4, nb + int(rng.integers(0, 2)))
-            out.append((59 + nb) << 2)
-            out += (n - 1).to_bytes(nb, "little")
-        out += lit[:n]
-        lit = lit[n:]
-
-
-def _snappy_copy(out, off, n, rng):
-    while n:
-        if 4 <= n <= 11 and off < 2048 and rng.random() < 0.6:
-            out.append(1 | ((n - 4) << 2) | ((off >> 8) << 5))
-            out.append(off & 255)
-            return
-        m = min(n, 64)
-        if n - m and n - m < 4:  # keep the remainder encodable (a copy of >= 1 byte is fine too)
-            m = n - 4 if n > 4 else n
-        if off < 65536 and rng.random() < 0.7:
-            out.append(2 | ((m - 1) << 2))
-            out += off.to_bytes(2, "little")
-        else:
-            out.append(3 | ((m - 1) << 2))
-            out += off.to_bytes(4, "little")
-        n -= m
-
-
-def _snappy_compress(data, rng):
-    out = bytearray(_varint(len(data)))
-    table, i, lit0, n = {}, 0, 0, len(data)
-    while i + 4 <= n:
-        key = data[i:i + 4]
-        j = table.get(key)
-        table[key] = i
-        if j is not None:
-            m = 4
-            while i + m < n and data[j + m] == data[i + m] and m < 300:
-                m += 1
-            _snappy_literal(out, data[lit0:i], rng)
-            _snappy_copy(out, i - j, m, rng)
-            i += m
-            lit0 = i
-        else:
-            i += 1
-    _snappy_literal(out, data[lit0:], rng)
-    return bytes(out)
-
-
-def _blosc_snappy_frame(data, ts, shuffle, blocksize, split, rng):
-    nbytes = len(data)
-    nblk = -(-nbytes // blocksize)
-    left = nbytes % blocksize
-    flags = (1 if shuffle else 0) | (0 if split else 0x10) | (2 << 5)
-    body, starts = bytearray(), []
-    hdr_len = 16 + 4 * nblk
-    for b in range(nblk):
-        src = data[b * blocksize:(b + 1) * blocksize]
-        bsize = len(src)
-        if shuffle and ts > 1:  # c-blosc shuffle: byte i of element j -> i * neb + j; the tail as is
-            neb = bsize // ts
-            a = np.frombuffer(src[:neb * ts], np.uint8).reshape(neb, ts).T.reshape(-1).tobytes()
-            src = a + src[neb * ts:]
-        nsplit = ts if (split and not (left and b == nblk - 1)) else 1
-        ne = bsize // nsplit
-        starts.append(hdr_len + len(body))
-        for j in range(nsplit):
-            part = src[j * ne:(j + 1) * ne]
-            z = _snappy_compress(part, rng)
-            if len(z) >= ne:
-                z = part  # stored
-            body += len(z).to_bytes(4, "little") + z
-    cbytes = hdr_len + len(body)
-    hdr = bytes([2, 1, flags, ts]) + nbytes.to_bytes(4, "little") + blocksize.to_bytes(4, "little") + \
-        cbytes.to_bytes(4, "little")
-    return hdr + b"".join(s.to_bytes(4, "little") for s in starts) + bytes(body)
-
-
+# reach the split's size is stored), in tests/blosc_frames.py. No snappy library is installed: checked by
+# round trip against the encoded data here, and against the reference executor of hand-built streams
+# in tests/test_gpu_blosc_frames.py.
 @pytest.mark.parametrize("ts,shuffle,split", [(1, False, False), (2, True, True), (4, True, False),
                                               (4, False, True), (8, True, True)])
 def test_blosc_snappy_streams(ctx, torch_cuda, ts, shuffle, split):

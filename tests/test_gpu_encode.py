@@ -483,6 +483,9 @@ BLOSC_CHAINS = {
     "zlib_shuffle_f32": ([B("little"), BL("zlib", "shuffle", 4)], "float32"),
     "zlib_bitshuffle_blocks_f32": ([B("little"), BL("zlib", "bitshuffle", 4, blocksize=24000)], "float32"),
     "zlib_noshuffle_crc_f32": ([B("little"), BL("zlib", "noshuffle", 4), {"name": "crc32c"}], "float32"),
+    # blocks of fewer than 128 elements: c-blosc's decoder never splits them, so the encoder must not
+    "lz4_shuffle_small_blocks_f32": ([B("little"), BL("lz4", "shuffle", 4, blocksize=256)], "float32"),
+    "blosclz_shuffle_small_blocks_f32": ([B("little"), BL("blosclz", "shuffle", 4, blocksize=500)], "float32"),
 }
 
 

@@ -1,4 +1,4 @@
-// blosc (c-blosc 1.x frame, format version 1/2) decode on gfx950: SURVEY.md §8(f) rank 2.
+// blosc (c-blosc 1.x frame, format version 2) decode on gfx950: SURVEY.md §8(f) rank 2.
 //
 // Reference: zarrs' blosc codec (zarrs/src/array/codec/bytes_to_bytes/blosc/blosc_codec_via_blosc_src.rs
 // :132-142 do_decode -> blosc_validate + blosc_decompress_bytes, blosc_via_blosc_src.rs:115-191), i.e.
@@ -7,7 +7,8 @@
 //   flags: 0x1 byte shuffle, 0x2 memcpyed (raw payload after the header), 0x4 bitshuffle,
 //          0x10 blocks not split, bits 5-7 compressor format (0 blosclz, 1 lz4/lz4hc, 2 snappy,
 //          3 zlib, 4 zstd); every one of them decodes here (formats 5-7 -> UNSUPPORTED)
-//   bstarts[nblocks] i32, then per block nsplit = (split && not the leftover block) ? typesize : 1
+//   bstarts[nblocks] i32, then per block nsplit = (split allowed && typesize <= 16 && blocksize /
+//   typesize >= 128 && not the leftover block) ? typesize : 1
 //   streams of {csize i32, payload}; csize == neblock means stored.
 // A block's streams concatenate to the shuffled block, then unshuffle / bitunshuffle (format 2:
 // only when the block's element count is a multiple of 8, else the block is stored unshuffled).
@@ -20,8 +21,12 @@
 //   k_blosc_streams  one wave per item: walks bstarts + split sizes in parallel over blocks, writes
 //                    one ZgItem per compressed stream (+ its kind) and one record per block
 //   zstd streams     the block-parallel zstd pipeline (launch_zstd) over the stream table
-//   k_lz4, k_blosclz, k_snappy  one wave per lz4 / blosclz / snappy stream (input staged through
-//                    an LDS window, recent output in an LDS ring)
+//   k_lz4m, k_blosclzm, k_snappym  lz4 / blosclz / snappy streams from a compacted list (k_lz_list),
+//                    two per wave (<32>), those of bitshuffled blocks one per wave (<64>); input staged
+//                    through an LDS window, recent output in an LDS ring. The one-wave kernels k_lz4,
+//                    k_blosclz, k_snappy and Lz32 are not reached by the default build (lz_list is always
+//                    allocated and ZG_LZM_G is 32): only -DZG_LZM_G=64 launches them, and the hand-built
+//                    frame tests (tests/test_gpu_blosc_frames.py) do not cover them
 //   zlib streams     k_gzip's DEFLATE decoder with the RFC 1950 wrapper (inflate.hip), then the
 //                    Adler-32 trailer check (k_adler32_check, crc.hip)
 //   k_blosc_finish   one workgroup per block: gathers the block's streams and unshuffles /
@@ -35,12 +40,18 @@ __device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) {
   return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 __device__ __forceinline__ void set_status(uint32_t *st, uint32_t v) { atomicCAS(st, 0u, v); }
+// Streams per full block (blosc_d): the flag only allows a split; c-blosc splits when typesize <= 16
+// (MAX_SPLITS) and the block holds at least 128 elements (MIN_BUFFERSIZE), as frames from before the
+// flag existed rely on. The leftover block is never split.
+__device__ __forceinline__ uint32_t bl_nsplit(uint32_t flags, uint32_t ts, uint32_t bs) {
+  return (!(flags & 0x10) && ts <= 16 && bs / ts >= 128) ? ts : 1u;
+}
 
 __global__ __launch_bounds__(64) void k_blosc_info(const ZgItem *items, uint32_t *status, uint32_t n_items,
                                                    uint64_t slot_bytes, BlInfo *info) {
   const uint32_t i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n_items) return;
-  BlInfo r{0, 0, BL_COMP_SKIP, 0, 0, 0};
+  BlInfo r{0, 0, BL_COMP_SKIP, 0, 0};
   const ZgItem it = items[i];
   if (status[i] || (it.flags & ZG_ITEM_FILL)) {
     info[i] = r;
@@ -49,38 +60,43 @@ __global__ __launch_bounds__(64) void k_blosc_info(const ZgItem *items, uint32_t
   const uint8_t *h = (const uint8_t *)it.src;
   uint32_t err = 0;
   if (it.len < 16) err = ZG_CORRUPT_STREAM;
-  uint32_t ver = 0, flags = 0, ts = 0, nbytes = 0, bs = 0, cbytes = 0;
+  uint32_t ver = 0, vlz = 0, flags = 0, ts = 0, nbytes = 0, bs = 0, cbytes = 0;
   if (!err) {
     ver = h[0];
+    vlz = h[1];
     flags = h[2];
     ts = h[3];
     nbytes = ld_u32(h + 4);
     bs = ld_u32(h + 8);
     cbytes = ld_u32(h + 12);
-    // blosc_cbuffer_validate: version, header cbytes within the buffer
-    if (ver > 2 || cbytes < 16 || cbytes > it.len) err = ZG_CORRUPT_STREAM;
+    // blosc_cbuffer_validate: format version 2, header cbytes within the buffer, typesize > 0,
+    // blocksize > 0. Two things c-blosc refuses are accepted here: bytes after
+    // the frame (cbytes below the buffer's length: a plan re-executed over rewritten device buffers
+    // keeps their lengths) and blocksize > nbytes (the frame is then its one leftover block; writers
+    // that do not clamp the block size, as the tests' snappy frame writer, emit it).
+    if (ver != 2 || cbytes < 16 || cbytes > it.len || ts == 0 || bs == 0) err = ZG_CORRUPT_STREAM;
     else if (nbytes > slot_bytes) err = ZG_DECODED_SIZE_MISMATCH;
   }
-  if (!err && (flags & 0x2)) {  // memcpyed: the payload is the data
-    if (16ull + nbytes > cbytes) err = ZG_CORRUPT_STREAM;
-    r = BlInfo{nbytes ? 1u : 0u, nbytes ? 1u : 0u, BL_COMP_MEMCPY, 0, nbytes, ver};
+  if (!err && (flags & 0x2)) {  // memcpyed: the payload is the data (compressor and its version unread)
+    if (16ull + nbytes != cbytes) err = ZG_CORRUPT_STREAM;
+    r = BlInfo{nbytes ? 1u : 0u, nbytes ? 1u : 0u, BL_COMP_MEMCPY, 0, nbytes};
   } else if (!err && nbytes) {
     const uint32_t comp = flags >> 5;
-    if (ts == 0 || bs == 0) err = ZG_CORRUPT_STREAM;
-    else if (comp > BL_COMP_ZSTD) err = ZG_UNSUPPORTED;  // formats 5-7 are not defined by c-blosc 1.x
+    if (comp > BL_COMP_ZSTD) err = ZG_UNSUPPORTED;  // formats 5-7 are not defined by c-blosc 1.x
+    else if (vlz != 1) err = ZG_CORRUPT_STREAM;     // every compressor's format version is 1
     if (!err) {
       const uint32_t lo = nbytes % bs, nfull = nbytes / bs, nblk = nfull + (lo ? 1 : 0);
-      const uint32_t nsplit = (flags & 0x10) ? 1 : ts;
+      const uint32_t nsplit = bl_nsplit(flags, ts, bs);
       if (16ull + 4ull * nblk > cbytes) err = ZG_CORRUPT_STREAM;
       const uint32_t ne = bs / nsplit;
-      r = BlInfo{nfull * nsplit + (lo ? 1 : 0), nblk, comp, ne > lo ? ne : lo, nbytes, ver};
+      r = BlInfo{nfull * nsplit + (lo ? 1 : 0), nblk, comp, ne > lo ? ne : lo, nbytes};
     }
   } else if (!err) {
-    r = BlInfo{0, 0, BL_COMP_MEMCPY, 0, 0, ver};
+    r = BlInfo{0, 0, BL_COMP_MEMCPY, 0, 0};
   }
   if (err) {
     status[i] = err;
-    r = BlInfo{0, 0, BL_COMP_SKIP, 0, 0, 0};
+    r = BlInfo{0, 0, BL_COMP_SKIP, 0, 0};
   }
   info[i] = r;
 }
@@ -138,7 +154,7 @@ __global__ __launch_bounds__(1024) void k_blosc_layout(const BlInfo *info, uint3
     sub_kind[k] = BL_KIND_RAW;
   }
   for (uint64_t k = over ? t : tot_blk + t; k < caps.n_blk; k += 1024)
-    blocks[k] = BlBlock{0, 0, 0, 0, 0, 0, 0, 1, 1};
+    blocks[k] = BlBlock{0, 0, 0, 0, 0, 0, 0, 1};
 }
 
 __global__ __launch_bounds__(64) void k_blosc_streams(ZgItem *items, uint32_t *status, const BlInfo *info,
@@ -163,12 +179,12 @@ __global__ __launch_bounds__(64) void k_blosc_streams(ZgItem *items, uint32_t *s
       subs[sub0] = ZgItem{it.src + 16, I.nbytes, item, 0, 0, 0};
       sub_status[sub0] = BL_SKIP;
       sub_kind[sub0] = BL_KIND_RAW;
-      blocks[blk0] = BlBlock{item, I.nbytes, 0, (uint32_t)sub0, 1, I.nbytes, 0, 1, I.ver};
+      blocks[blk0] = BlBlock{item, I.nbytes, 0, (uint32_t)sub0, 1, I.nbytes, 0, 1};
       n_dec = 1;
     }
   } else {
     const uint32_t flags = h[2], ts = h[3], bs = ld_u32(h + 8), cbytes = ld_u32(h + 12);
-    const uint32_t lo = I.nbytes % bs, nsplit_full = (flags & 0x10) ? 1 : ts;
+    const uint32_t lo = I.nbytes % bs, nsplit_full = bl_nsplit(flags, ts, bs);
     const uint32_t mode = ((flags & 0x1) && ts > 1) ? 1u : (flags & 0x4) ? 2u : 0u;
     blk_bytes = bs;
     for (uint32_t b = lane; b < I.nblk; b += 64) {
@@ -181,7 +197,7 @@ __global__ __launch_bounds__(64) void k_blosc_streams(ZgItem *items, uint32_t *s
         sub_kind[s0 + j] = BL_KIND_RAW;
       }
       if ((uint64_t)b * bs >= nhi || (uint64_t)b * bs + bsize <= nlo) {  // not read by the selection
-        blocks[blk0 + b] = BlBlock{item, 0u, (uint64_t)b * bs, (uint32_t)s0, 0u, ne, mode, ts, I.ver};
+        blocks[blk0 + b] = BlBlock{item, 0u, (uint64_t)b * bs, (uint32_t)s0, 0u, ne, mode, ts};
         continue;
       }
       n_dec++;
@@ -214,7 +230,7 @@ __global__ __launch_bounds__(64) void k_blosc_streams(ZgItem *items, uint32_t *s
       }
       if (!ok) bad = true;
       blocks[blk0 + b] = BlBlock{item, ok ? bsize : 0u, (uint64_t)b * bs, (uint32_t)s0, ok ? nsplit : 0u, ne, mode,
-                                 ts, I.ver};
+                                 ts};
     }
   }
   bad = __any(bad);
@@ -1001,7 +1017,7 @@ __global__ __launch_bounds__(256) void k_blosc_finish(const BlBlock *blocks, con
     }
   } else if (B.mode == 2 && bsize >= ts) {  // bitunshuffle (bshuf_untrans_bit_elem)
     const uint32_t size = bsize / ts;
-    const uint32_t n8 = (B.ver == 2) ? ((size % 8) ? 0u : size) : size - size % 8;
+    const uint32_t n8 = (size % 8) ? 0u : size;  // format 2: only whole multiples of 8 elements
     const uint32_t body = n8 * ts, rb = n8 / 8;  // rb: bytes per bit-row
     // Element j, byte b, bit k is bit j of bit-row 8b + k. A thread takes 8 elements (column byte g
     // of every row: coalesced across the threads) and per output byte b transposes the 8x8 bit

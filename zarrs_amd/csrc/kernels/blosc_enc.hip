@@ -492,9 +492,10 @@ BloscEnc blosc_enc_params(uint32_t comp, uint32_t shuffle, uint32_t ts, uint64_t
   E.bs = bs;
   E.nblk = (uint32_t)(nbytes ? (nbytes + bs - 1) / bs : 0);
   // split the byte-shuffled planes into streams of their own (c-blosc's forward-compatible rule for
-  // its LZ compressors); zstd streams stay whole
+  // its LZ compressors); zstd streams stay whole. c-blosc's decoder splits only blocks of at least 128
+  // elements (blosc_d), whatever the header's flag says
   E.nsplit = (E.shuffle == 1 && (comp == BL_COMP_LZ4 || comp == BL_COMP_BLOSCLZ || comp == BL_COMP_SNAPPY) &&
-              E.ts <= 16 && bs % E.ts == 0)
+              E.ts <= 16 && bs % E.ts == 0 && bs / E.ts >= 128)
                  ? E.ts : 1u;
   const uint32_t nfull = (uint32_t)(nbytes / bs);
   E.spi = nfull * E.nsplit + ((nbytes % bs) ? 1u : 0u);

@@ -273,12 +273,11 @@ struct BlInfo {     // per item (read back)
   uint32_t comp;    // BL_COMP_*
   uint32_t max_ne;  // largest stream decoded size
   uint32_t nbytes;  // decoded size
-  uint32_t ver;     // frame format version
 };
 struct BlBlock {
   uint32_t item, bsize;
   uint64_t out_off;  // in the item's decoded bytes
-  uint32_t first_sub, nsplit, ne, mode, ts, ver;  // mode 0 none, 1 byte unshuffle, 2 bitunshuffle
+  uint32_t first_sub, nsplit, ne, mode, ts;  // mode 0 none, 1 byte unshuffle, 2 bitunshuffle
 };
 constexpr uint32_t BL_SUB_WIDE = 0x80000000u;  // stream ZgItem flag: decode it with a whole wave
 struct BlDecode {
