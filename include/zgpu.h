@@ -266,6 +266,16 @@ void zgpu_plan_destroy(zgpu_plan *plan);
 /* Algorithmic HBM bytes of one execute (encoded bytes read + index bytes + decoded bytes
  * written), the figure bench.py prices the roofline with. */
 uint64_t zgpu_plan_algorithmic_bytes(const zgpu_plan *plan);
+/* The scatter kernel of the plan's last execute (before the first: the one the plan is eligible for).
+ * Uniform batches of whole chunks of a transposing chain (full 64-wide tiles on 16-byte aligned
+ * rows) take the tiled kernel that works from per-plan constants, ZGPU_SCATTER_TILED_PERSISTENT
+ * (ZGPU_TILED_PERSIST=0 in the environment keeps the general tiled kernel; ZGPU_TILED_GRID=n makes n
+ * workgroups loop over the batch instead of one workgroup per tile group). */
+#define ZGPU_SCATTER_ROWS 0u
+#define ZGPU_SCATTER_TILED 1u
+#define ZGPU_SCATTER_GENERIC 2u
+#define ZGPU_SCATTER_TILED_PERSISTENT 3u
+uint32_t zgpu_plan_scatter_path(const zgpu_plan *plan);
 
 /*
  * Plan group: one decode over the independent parts of a batch, each part one chunk shape and one

@@ -44,8 +44,9 @@ EXPORTS = [
     "zgpu_ctx_coalescing_stats", "zgpu_ctx_refcount", "zgpu_decode_pinned", "zgpu_result_release",
     "zgpu_encode_pinned", "zgpu_ctx_release_cached", "zgpu_ctx_pool_stats",
     "zgpu_group_create", "zgpu_group_execute", "zgpu_group_status", "zgpu_group_layout",
-    "zgpu_group_algorithmic_bytes", "zgpu_group_counters", "zgpu_group_destroy",
+    "zgpu_group_algorithmic_bytes", "zgpu_group_counters", "zgpu_group_destroy", "zgpu_plan_scatter_path",
 ]
+SCATTER_ROWS, SCATTER_TILED, SCATTER_GENERIC, SCATTER_TILED_PERSISTENT = range(4)  # zgpu_plan_scatter_path
 CTR_ENC_BYTES, CTR_ZSTD_SERIAL, CTR_ZSTD_PARALLEL, CTR_BLOSC_RERUN, CTR_BLOSC_BLOCKS, CTR_ITEMS, \
     CTR_ZSTD_LATENCY = range(7)
 N_COUNTERS = 7
@@ -157,6 +158,8 @@ def load() -> C.CDLL:
     L.zgpu_plan_destroy.argtypes = [vp]
     L.zgpu_plan_algorithmic_bytes.restype = u64
     L.zgpu_plan_algorithmic_bytes.argtypes = [vp]
+    L.zgpu_plan_scatter_path.restype = u32
+    L.zgpu_plan_scatter_path.argtypes = [vp]
     L.zgpu_group_create.argtypes = [C.POINTER(vp), u32, u32, C.POINTER(C.POINTER(ChunkDesc)), P64, C.POINTER(P64),
                                     u32, C.POINTER(vp)]
     L.zgpu_group_execute.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), vp]

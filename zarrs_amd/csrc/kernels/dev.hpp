@@ -26,6 +26,14 @@ __device__ __forceinline__ uint4 nt_load16(const void *p) {
   const zg_v4u x = __builtin_nontemporal_load((const zg_v4u *)p);
   return make_uint4(x.x, x.y, x.z, x.w);
 }
+// The same load from an address known to be global memory (an item's src is a device address held
+// as an integer, which the compiler can only treat as a generic pointer: a flat load, counted as an
+// LDS operation too, so every wait for LDS then waits for the loads in flight as well).
+__device__ __forceinline__ uint4 nt_load16_g(const void *p) {
+  typedef const zg_v4u __attribute__((address_space(1))) *gptr;
+  const zg_v4u x = __builtin_nontemporal_load((gptr)(uintptr_t)p);
+  return make_uint4(x.x, x.y, x.z, x.w);
+}
 __device__ __forceinline__ void nt_store16(void *p, uint4 v) {
   const zg_v4u x = {v.x, v.y, v.z, v.w};
   __builtin_nontemporal_store(x, (zg_v4u *)p);

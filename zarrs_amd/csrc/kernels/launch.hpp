@@ -44,6 +44,31 @@ hipError_t launch_scatter(const ZgItem *items, const uint64_t *geom, uint32_t *s
                                                                             // over the items not yet written
 uint64_t scatter_units_per_item(uint32_t mode, const ZgScatter &P, const uint64_t *max_sel_shape);
 
+// Tiled scatter of uniform whole-chunk batches (k_scatter_tiled_p): per-plan constants of a batch
+// whose every item is a whole chunk of full TILE x TILE tiles on 16-B aligned rows. Strides in
+// elements; every offset inside a chunk and inside an item's output box fits 32 bits
+// (tiled_persistent_params checks all of it).
+struct ZgTiledP {
+  uint32_t upi;                 // units per item (= scatter_units_per_item)
+  uint32_t nta, ntl, nbg;       // tiles along A and Lx, slab groups along B
+  uint32_t bext;                // extent of B (1: no B axis)
+  uint32_t sL, sB, dA, dB;      // encoded stride of Lx and B, output stride of A and B
+  uint32_t nrest;               // the other axes, innermost first: extent, encoded and output stride
+  uint32_t rext[ZG_MAXD], rs[ZG_MAXD], rd[ZG_MAXD];
+};
+// false: the batch is not eligible (it keeps the one-unit-per-block kernel). geom: per item sel_start |
+// sel_shape | out_start (3 * nd); origin[i] receives the output element offset of item i's origin.
+bool tiled_persistent_params(const ZgScatter &P, const uint64_t *geom, size_t n_items, ZgTiledP &Q,
+                             uint64_t *origin);
+// grid_cap: 0 (one workgroup per unit, as far as one launch goes), or the most workgroups to launch,
+// which then loop over the units (ZGPU_TILED_GRID: tests make a few loop over many). Returns
+// hipErrorInvalidConfiguration when the unit count does not fit the kernel's 32-bit unit index.
+hipError_t launch_scatter_tiled_p(const ZgItem *items, const uint64_t *geom, uint32_t *status, const uint64_t *origin,
+                                  const ZgScatter &P, const ZgTiledP &Q, uint8_t *out, uint32_t n_items,
+                                  uint32_t grid_cap, hipStream_t s);
+// whether n_items x upi units fit launch_scatter_tiled_p
+bool tiled_persistent_fits(uint64_t n_items, uint64_t upi);
+
 // Box copy between device arrays: run r (C order over the `outer` axes of `shape`) is run_bytes
 // contiguous bytes at src_base + sum(c_d * src_stride[d]) -> dst_base + sum(c_d * dst_stride[d]).
 struct ZgBoxCopy {

@@ -340,19 +340,30 @@ __global__ __launch_bounds__(SCATTER_THREADS) void k_scatter_rows_list(
 // ---------------------------------------------------------------------------------------------
 constexpr int TILE = 64;
 
+// Element type, slab count and LDS layout of the tiled kernels for ES-byte elements.
 template <int ES>
-__global__ __launch_bounds__(SCATTER_THREADS) void k_scatter_tiled(
-    const ZgItem *__restrict__ items, const uint64_t *__restrict__ geom, uint32_t *__restrict__ status,
-    ZgScatter P, uint8_t *__restrict__ out, uint32_t tiles_per_item, uint64_t block_base) {
+struct Tiled {
   using T = typename std::conditional<ES == 1, uint8_t, typename std::conditional<ES == 2, uint16_t,
             typename std::conditional<ES == 4, uint32_t, uint2>::type>::type>::type;
-  constexpr int TJ = tiled_slabs(ES);
-  constexpr int PITCH = TILE + (ES >= 4 ? 1 : 4 / ES);  // +1 word: column reads conflict-free
-  constexpr int SLAB = TILE * PITCH + (ES >= 4 ? 1 : 4 / ES);  // +1 word: slabs on distinct banks
-  __shared__ T tile[TJ * SLAB];
-  const uint64_t bid = block_base + blockIdx.x;
-  const uint32_t item = (uint32_t)(bid / tiles_per_item);
-  uint32_t t = (uint32_t)(bid % tiles_per_item);
+  static constexpr int TJ = tiled_slabs(ES);
+  static constexpr int PITCH = TILE + (ES >= 4 ? 1 : 4 / ES);  // +1 word: column reads conflict-free
+  static constexpr int SLAB = TILE * PITCH + (ES >= 4 ? 1 : 4 / ES);  // +1 word: slabs on distinct banks
+  static constexpr int VPR = TILE * ES / 16;  // 16-B vectors per tile row
+  static constexpr int EPV = 16 / ES;         // elements per vector
+  static constexpr int NV = TJ * TILE * VPR;  // vectors per block
+  static constexpr int PER = NV / SCATTER_THREADS;  // vectors per thread
+};
+
+// One (item, TJ slabs of one tile) unit of the tiled scatter through the block's LDS tile (TJ * SLAB
+// elements); every early exit is block-uniform. Run-time geometry: partial selections, ragged tiles,
+// fill items and unaligned rows (element-wise) all go through here.
+template <int ES>
+__device__ __forceinline__ void tiled_unit(const ZgItem *__restrict__ items, const uint64_t *__restrict__ geom,
+                                           uint32_t *__restrict__ status, const ZgScatter &P,
+                                           uint8_t *__restrict__ out, typename Tiled<ES>::T *tile, uint32_t item,
+                                           uint32_t t) {
+  using T = typename Tiled<ES>::T;
+  constexpr int TJ = Tiled<ES>::TJ, PITCH = Tiled<ES>::PITCH, SLAB = Tiled<ES>::SLAB;
   const ZgItem it = items[item];
   if (!item_live(it, status, item, P)) return;
   const uint32_t nd = P.nd, A = P.tile_a, Lx = nd - 1, B = P.tile_b;
@@ -383,9 +394,7 @@ __global__ __launch_bounds__(SCATTER_THREADS) void k_scatter_tiled(
   so += (ss[A] + a0) * P.enc_stride[A] + (ss[Lx] + l0) * sL + (hasB ? (ss[B] + b0) * sB : 0);
   dof += (os[A] + a0) * dA + (os[Lx] + l0) + (hasB ? (os[B] + b0) * dB : 0);
   T *dst = (T *)(out) + dof;
-  constexpr int VPR = TILE * ES / 16;  // 16-B vectors per tile row
-  constexpr int EPV = 16 / ES;         // elements per vector
-  constexpr int NV = TJ * TILE * VPR;  // vectors per block
+  constexpr int VPR = Tiled<ES>::VPR, EPV = Tiled<ES>::EPV, NV = Tiled<ES>::NV;
   const bool oaligned = (((uint64_t)dst & 15) == 0) && ((dA * ES) % 16 == 0) && ((dB * ES) % 16 == 0) &&
                         nl == TILE;
   if (it.flags & ZG_ITEM_FILL) {
@@ -420,7 +429,7 @@ __global__ __launch_bounds__(SCATTER_THREADS) void k_scatter_tiled(
     for (int p = 0; p < PER; p++) {
       const uint32_t e = p * SCATTER_THREADS + threadIdx.x;
       const uint32_t l = e / (TJ * VPR), jj = (e / VPR) % TJ, v = e % VPR;
-      if (l < nl && jj < nb) x[p] = nt_load16(src + jj * sB + (uint64_t)l * sL + v * EPV);
+      if (l < nl && jj < nb) x[p] = nt_load16_g(src + jj * sB + (uint64_t)l * sL + v * EPV);
     }
 #pragma unroll
     for (int p = 0; p < PER; p++) {
@@ -462,6 +471,210 @@ __global__ __launch_bounds__(SCATTER_THREADS) void k_scatter_tiled(
     for (uint32_t e = threadIdx.x; e < (uint32_t)(TJ * TILE * TILE); e += SCATTER_THREADS) {
       const uint32_t a = e / (TJ * TILE), jj = (e / TILE) % TJ, l = e % TILE;
       if (a < na && jj < nb && l < nl) dst[jj * dB + (uint64_t)a * dA + l] = tile[jj * SLAB + l * PITCH + a];
+    }
+  }
+}
+
+template <int ES>
+__global__ __launch_bounds__(SCATTER_THREADS) void k_scatter_tiled(
+    const ZgItem *__restrict__ items, const uint64_t *__restrict__ geom, uint32_t *__restrict__ status,
+    ZgScatter P, uint8_t *__restrict__ out, uint32_t tiles_per_item, uint64_t block_base) {
+  __shared__ typename Tiled<ES>::T tile[Tiled<ES>::TJ * Tiled<ES>::SLAB];
+  const uint64_t bid = block_base + blockIdx.x;
+  tiled_unit<ES>(items, geom, status, P, out, tile, (uint32_t)(bid / tiles_per_item),
+                 (uint32_t)(bid % tiles_per_item));
+}
+
+// ---------------------------------------------------------------------------------------------
+// Tiled transpose for batches of whole chunks (ZgTiledP, checked on the host: every item its whole
+// chunk, A and Lx extents multiples of TILE, every tile row 16-B aligned, offsets inside a chunk and
+// inside an item's output box below 2^32). Ahead of its data a unit reads only the item record, its
+// status and the output offset of its origin (one round trip, no geom); its coordinates are 32-bit
+// arithmetic on kernel arguments, and its loads are global, not flat. k_scatter_tiled's prologue (two
+// dependent round trips, then nine u64 of geom and eight 64-bit divisions) held one of a CU's two
+// workgroup slots idle for a fifth of a workgroup's life: C2 1.50 -> 1.45 ms per step.
+// The default grid is one workgroup per unit. A smaller grid (ZGPU_TILED_GRID, and batches beyond one
+// launch's grid) strides over the units (unit = workgroup + n * grid) with the loads of unit n+1 in
+// flight while unit n goes from LDS to the output and the record of unit n+2 fetched meanwhile. That
+// persistent form measured slower on C2 (1.58 ms with two workgroups per CU, 1.515 with one: the
+// copy is HBM-bound, and more bytes in flight per CU did not help), so it is not the default.
+// A unit that is not on the fast path (fill item, src not 16-B aligned: a shard resolves src on the
+// device) runs tiled_unit after the workgroup's fast units; the choice is block-uniform.
+// ---------------------------------------------------------------------------------------------
+template <int ES>
+__global__ __launch_bounds__(SCATTER_THREADS, 2) void k_scatter_tiled_p(
+    const ZgItem *__restrict__ items, const uint64_t *__restrict__ geom, uint32_t *__restrict__ status,
+    const uint64_t *__restrict__ origin, ZgScatter P, ZgTiledP Q, uint8_t *__restrict__ out, uint32_t n_units) {
+  using T = typename Tiled<ES>::T;
+  constexpr int TJ = Tiled<ES>::TJ, PITCH = Tiled<ES>::PITCH, SLAB = Tiled<ES>::SLAB;
+  constexpr int VPR = Tiled<ES>::VPR, EPV = Tiled<ES>::EPV, PER = Tiled<ES>::PER;
+  __shared__ T tile[TJ * SLAB];
+  enum : uint32_t { SKIP = 0, FAST = 1, SLOW = 2, MISMATCH = 3 };
+  struct Raw {  // what a unit reads ahead of its data
+    uint64_t src, len, org;
+    uint32_t flags, st;
+  };
+  struct Unit {
+    const T *src;
+    T *dst;
+    uint32_t nb, kind, item, t;
+  };
+  const uint64_t want = P.nelem * ES;
+  auto fetch = [&](uint32_t u) {
+    const uint32_t item = u / Q.upi;
+    Raw r;
+    r.src = items[item].src;
+    r.len = items[item].len;
+    r.flags = items[item].flags;
+    r.st = status[item];
+    r.org = origin[item];
+    return r;
+  };
+  auto resolve = [&](const Raw &r, uint32_t u) {
+    Unit U;
+    U.item = u / Q.upi;
+    uint32_t t = u - U.item * Q.upi;
+    U.t = t;
+    U.src = nullptr;
+    U.dst = nullptr;
+    U.nb = 0;
+    if (r.st || (r.flags & ZG_ITEM_DIRECT)) {
+      U.kind = SKIP;
+      return U;
+    }
+    if (!(r.flags & ZG_ITEM_FILL) && r.len != want) {
+      U.kind = MISMATCH;  // reported by the caller (aside)
+      return U;
+    }
+    if ((r.flags & ZG_ITEM_FILL) || (r.src & 15)) {
+      U.kind = SLOW;
+      return U;
+    }
+    const uint32_t ta = t % Q.nta; t /= Q.nta;
+    const uint32_t tl = t % Q.ntl; t /= Q.ntl;
+    const uint32_t tb = t % Q.nbg; t /= Q.nbg;
+    uint32_t so = ta * TILE + tl * TILE * Q.sL + tb * TJ * Q.sB;
+    uint32_t dof = ta * TILE * Q.dA + tl * TILE + tb * TJ * Q.dB;
+    for (uint32_t k = 0; k < Q.nrest; k++) {
+      const uint32_t c = t % Q.rext[k];
+      t /= Q.rext[k];
+      so += c * Q.rs[k];
+      dof += c * Q.rd[k];
+    }
+    U.kind = FAST;
+    U.nb = min((uint32_t)TJ, Q.bext - tb * TJ);
+    U.src = (const T *)r.src + so;
+    U.dst = (T *)out + r.org + dof;
+    return U;
+  };
+  uint4 x[PER];
+  // vector e = p * SCATTER_THREADS + thread -> (row l, slab jj, vector v): a wave reads TJ adjacent
+  // encoded rows = one contiguous run. A thread keeps its slab and vector and moves RSTEP rows per p,
+  // so its addresses are one base and a running stride. The threads of a slab past a ragged group's
+  // end (jj >= nb) move the group's last slab once more (the same bytes to the same addresses), so
+  // the pipeline has no divergent branch and its loads, stores and waits stay in one basic block
+  constexpr uint32_t RSTEP = SCATTER_THREADS / (TJ * VPR);
+  const uint32_t r0 = threadIdx.x / (TJ * VPR), jj = (threadIdx.x / VPR) % TJ, v = threadIdx.x % VPR;
+  auto load = [&](const Unit &U) {
+    const T *q = U.src + min(jj, U.nb - 1) * Q.sB + r0 * Q.sL + v * EPV;
+#pragma unroll
+    for (int p = 0; p < PER; p++, q += RSTEP * Q.sL) x[p] = nt_load16_g(q);
+  };
+  auto to_lds = [&](auto cc) {  // cc: the component size to reverse (1: none), a compile-time constant
+    constexpr uint32_t COMP = decltype(cc)::value;
+#pragma unroll
+    for (int p = 0; p < PER; p++) {
+      const uint32_t l = p * RSTEP + r0;
+      const uint4 y = COMP > 1 ? swap_vec(x[p], COMP) : x[p];
+      const T *ye = (const T *)&y;
+#pragma unroll
+      for (int k = 0; k < EPV; k++) tile[jj * SLAB + l * PITCH + v * EPV + k] = ye[k];
+    }
+  };
+  auto store = [&](const Unit &U) {
+    T *q = U.dst + min(jj, U.nb - 1) * Q.dB + r0 * Q.dA + v * EPV;
+#pragma unroll
+    for (int p = 0; p < PER; p++, q += RSTEP * Q.dA) {
+      const uint32_t a = p * RSTEP + r0;
+      uint4 y;
+      T *ye = (T *)&y;
+#pragma unroll
+      for (int k = 0; k < EPV; k++) ye[k] = tile[jj * SLAB + (v * EPV + k) * PITCH + a];
+      nt_store16(q, y);
+    }
+  };
+  const uint32_t first = blockIdx.x, step = gridDim.x, end = n_units;
+  uint32_t any_slow = 0;
+  auto aside = [&](const Unit &U) {  // a unit the pipeline does not take
+    if (U.kind == SLOW) any_slow = 1;
+    if (U.kind == MISMATCH && threadIdx.x == 0) status[U.item] = ZG_DECODED_SIZE_MISMATCH;
+  };
+  // Runs of fast units: the first one's tile is in LDS before the steady loop, which per unit issues
+  // the next unit's loads, stores this unit from LDS, resolves the unit after the next (its record
+  // was fetched an iteration ago; the index is clamped, so the fetch is unconditional) and moves the
+  // loaded registers to LDS. Nothing but the barrier stands between a free tile and the next loads.
+  // n_units < 2^32 - 2^24 (checked at launch): un + step does not wrap
+  auto run = [&](auto cc) {
+    uint32_t un = first;
+    Raw ahead = fetch(min(un, end - 1));
+    while (un < end) {
+      Unit cur = resolve(ahead, un);
+      un += step;
+      ahead = fetch(min(un, end - 1));
+      if (cur.kind != FAST) {
+        aside(cur);
+        continue;
+      }
+      load(cur);
+      Unit nxt{};
+      bool more = un < end;  // nxt is a unit
+      if (more) {
+        nxt = resolve(ahead, un);
+        un += step;
+        ahead = fetch(min(un, end - 1));
+      }
+      to_lds(cc);
+      __syncthreads();
+      for (;;) {
+        if (nxt.kind != FAST) {  // the run ends here (also after the last unit: nxt.kind == SKIP)
+          store(cur);
+          __syncthreads();
+          if (more) aside(nxt);
+          break;
+        }
+        load(nxt);
+        store(cur);
+        Unit nn{};
+        const bool more2 = un < end;
+        if (more2) {
+          nn = resolve(ahead, un);
+          un += step;
+          ahead = fetch(min(un, end - 1));
+        }
+        __syncthreads();  // the tile is free
+        to_lds(cc);
+        __syncthreads();
+        cur = nxt;
+        nxt = nn;
+        more = more2;
+      }
+    }
+  };
+  switch (P.swap ? P.comp : 1u) {
+    case 2: run(std::integral_constant<uint32_t, 2>{}); break;
+    case 4: run(std::integral_constant<uint32_t, 4>{}); break;
+    case 8: run(std::integral_constant<uint32_t, 8>{}); break;
+    default: run(std::integral_constant<uint32_t, 1>{});
+  }
+  if (any_slow) {
+    // the units left aside (fill items, src not 16-B aligned) through the general body, after the
+    // pipeline so that its registers and the body's are never live together
+    for (uint32_t u = first; u < end; u += step) {
+      const uint32_t item = u / Q.upi;
+      if ((items[item].flags & ZG_ITEM_FILL) || (items[item].src & 15)) {
+        tiled_unit<ES>(items, geom, status, P, out, tile, item, u - item * Q.upi);
+        __syncthreads();  // the tile is free for the next unit
+      }
     }
   }
 }
@@ -580,6 +793,83 @@ uint64_t scatter_units_per_item(uint32_t mode, const ZgScatter &P, const uint64_
   uint64_t n = 1;
   for (uint32_t d = 0; d < nd; d++) n *= max_sel_shape[d];
   return (n + SCATTER_THREADS - 1) / SCATTER_THREADS;
+}
+
+bool tiled_persistent_params(const ZgScatter &P, const uint64_t *geom, size_t n_items, ZgTiledP &Q,
+                             uint64_t *origin) {
+  const uint32_t nd = P.nd, A = P.tile_a, Lx = nd - 1, B = P.tile_b, es = P.es;
+  if (!n_items || A >= nd || A == Lx || P.shuffle || !P.nelem || P.nelem >= (1ull << 32)) return false;
+  if (es != 1 && es != 2 && es != 4 && es != 8) return false;
+  if (P.enc_stride[A] != 1 || P.out_stride[Lx] != 1) return false;
+  if (P.chunk_shape[A] % TILE || P.chunk_shape[Lx] % TILE) return false;
+  uint64_t span = 0;  // the last element of an item's output box, from its origin
+  for (uint32_t d = 0; d < nd; d++) {
+    const uint64_t ext = P.chunk_shape[d];
+    span += (ext - 1) * P.out_stride[d];
+    if (ext > 1 && d != A && (P.enc_stride[d] * es) % 16) return false;
+    if (ext > 1 && d != Lx && (P.out_stride[d] * es) % 16) return false;
+  }
+  if (span >= (1ull << 32)) return false;
+  for (size_t i = 0; i < n_items; i++) {
+    const uint64_t *g = geom + i * 3 * nd;
+    uint64_t o = 0;
+    for (uint32_t d = 0; d < nd; d++) {
+      if (g[d] != 0 || g[nd + d] != P.chunk_shape[d]) return false;
+      o += g[2 * nd + d] * P.out_stride[d];
+    }
+    if ((o * es) % 16) return false;
+    origin[i] = o;
+  }
+  const bool hasB = B < nd;
+  const uint32_t tj = (uint32_t)tiled_slabs(es);
+  Q = ZgTiledP{};
+  Q.nta = (uint32_t)(P.chunk_shape[A] / TILE);
+  Q.ntl = (uint32_t)(P.chunk_shape[Lx] / TILE);
+  Q.bext = hasB ? (uint32_t)P.chunk_shape[B] : 1;
+  Q.nbg = (Q.bext + tj - 1) / tj;
+  Q.sL = (uint32_t)P.enc_stride[Lx];
+  Q.dA = (uint32_t)P.out_stride[A];
+  Q.sB = Q.bext > 1 ? (uint32_t)P.enc_stride[B] : 0;
+  Q.dB = Q.bext > 1 ? (uint32_t)P.out_stride[B] : 0;
+  uint64_t upi = (uint64_t)Q.nta * Q.ntl * Q.nbg;
+  for (int d = (int)nd - 1; d >= 0; d--) {
+    if ((uint32_t)d == A || (uint32_t)d == Lx || (uint32_t)d == B) continue;
+    const uint32_t k = Q.nrest++;
+    Q.rext[k] = (uint32_t)P.chunk_shape[d];
+    Q.rs[k] = Q.rext[k] > 1 ? (uint32_t)P.enc_stride[d] : 0;
+    Q.rd[k] = Q.rext[k] > 1 ? (uint32_t)P.out_stride[d] : 0;
+    upi *= Q.rext[k];
+  }
+  if (upi >= (1ull << 32)) return false;
+  Q.upi = (uint32_t)upi;
+  return true;
+}
+
+bool tiled_persistent_fits(uint64_t n_items, uint64_t upi) { return n_items * upi < 0xFFFFFFFFull - (1u << 24); }
+
+template <int ES>
+static void launch_tiled_p(const ZgItem *items, const uint64_t *geom, uint32_t *status, const uint64_t *origin,
+                           const ZgScatter &P, const ZgTiledP &Q, uint8_t *out, uint32_t n_units, uint32_t grid_cap,
+                           hipStream_t s) {
+  uint64_t g = std::min<uint64_t>(n_units, max_grid_blocks(SCATTER_THREADS));
+  if (grid_cap) g = std::min<uint64_t>(g, grid_cap);
+  hipLaunchKernelGGL(k_scatter_tiled_p<ES>, dim3((uint32_t)g), dim3(SCATTER_THREADS), 0, s, items, geom, status, origin,
+                     P, Q, out, n_units);
+}
+
+hipError_t launch_scatter_tiled_p(const ZgItem *items, const uint64_t *geom, uint32_t *status, const uint64_t *origin,
+                                  const ZgScatter &P, const ZgTiledP &Q, uint8_t *out, uint32_t n_items,
+                                  uint32_t grid_cap, hipStream_t s) {
+  if (!n_items || !Q.upi || !tiled_persistent_fits(n_items, Q.upi)) return hipErrorInvalidConfiguration;
+  const uint32_t n_units = n_items * Q.upi;
+  switch (P.es) {
+    case 1: launch_tiled_p<1>(items, geom, status, origin, P, Q, out, n_units, grid_cap, s); break;
+    case 2: launch_tiled_p<2>(items, geom, status, origin, P, Q, out, n_units, grid_cap, s); break;
+    case 4: launch_tiled_p<4>(items, geom, status, origin, P, Q, out, n_units, grid_cap, s); break;
+    case 8: launch_tiled_p<8>(items, geom, status, origin, P, Q, out, n_units, grid_cap, s); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
 }
 
 }  // namespace zgpu

@@ -414,6 +414,14 @@ struct zgpu_plan {
   // back by ONE D2H copy into pinned memory (h_ctl) per execute
   uint8_t *d_ctl = nullptr, *h_ctl = nullptr;
   size_t ctl_bytes = 0;
+  // A tiled plan whose every item is a whole chunk of full, 16-B aligned tiles scatters with
+  // k_scatter_tiled_p (tiled_persistent_params; ZGPU_TILED_PERSIST=0: k_scatter_tiled): its constants
+  // and the output element offset of each item's origin
+  bool tiled_p = false;
+  ZgTiledP tiled_q{};
+  std::vector<uint64_t> origin;
+  uint64_t *d_origin = nullptr;
+  uint32_t last_path = SCATTER_GENERIC;  // zgpu_plan_scatter_path: of the last enqueue (before one: the plan's)
   // host-input staging
   uint8_t *d_enc_stage = nullptr;
   uint64_t last_enc_bytes = 0;
@@ -450,7 +458,7 @@ struct zgpu_plan {
     void *bufs[] = {d_items, d_items_init, d_geom, d_shards, d_index, d_shard_status, d_mids, d_mids_init,
                     d_mid_status, d_shard_status2, d_mid_shards, d_index2, d_bl_need,
                     d_pool[0], d_pool[1], zs.blks, zs.nblk, zs.mode, zs.lit, zs.seq, d_ctl,
-                    d_enc_stage, d_zser, d_order, d_gz_seg, zs.lit_rec, zs.ext, zs.ext_cnt, zs.norm};
+                    d_enc_stage, d_zser, d_order, d_gz_seg, zs.lit_rec, zs.ext, zs.ext_cnt, zs.norm, d_origin};
     for (void *b : bufs) ctx->dev_free(b);
     if (zside) {
       (void)hipStreamSynchronize(zside);
@@ -851,6 +859,13 @@ static void plan_build(zgpu_plan &P, const zgpu_chunk_desc *descs) {
     P.scatter_mode = SCATTER_GENERIC;
   }
   P.scatter_units = P.items.empty() ? 0 : scatter_units_per_item(P.scatter_mode, S, max_sel);
+  if (P.scatter_mode == SCATTER_TILED && !P.items.empty()) {
+    P.origin.resize(P.items.size());
+    P.tiled_p = tiled_persistent_params(S, P.geom.data(), P.items.size(), P.tiled_q, P.origin.data()) &&
+                P.tiled_q.upi == P.scatter_units && tiled_persistent_fits(P.items.size(), P.tiled_q.upi);
+    if (!P.tiled_p) P.origin.clear();
+  }
+  P.last_path = P.tiled_p ? ZGPU_SCATTER_TILED_PERSISTENT : P.scatter_mode;
 
   // blosc as the last stage feeding the rows scatter unchanged (no swap / shuffle / transpose), every
   // decoded item a whole chunk on 16-B aligned output rows: k_blosc_finish writes the rows itself
@@ -989,6 +1004,10 @@ static void plan_upload(zgpu_plan &P, hipStream_t us) {
   P.ctl_bytes = 256 + ni * 4;
   P.d_ctl = (uint8_t *)C.dev_alloc(P.ctl_bytes);
   P.h_ctl = (uint8_t *)C.host_alloc(P.ctl_bytes);
+  if (P.tiled_p) {
+    P.d_origin = (uint64_t *)C.dev_alloc(ni * 8);
+    HIPCHK(hipMemcpyAsync(P.d_origin, P.origin.data(), ni * 8, hipMemcpyHostToDevice, us));
+  }
   P.d_counter = (unsigned long long *)P.d_ctl;
   P.d_status = (uint32_t *)(P.d_ctl + 256);
   P.zs.counters = P.d_counter + CTR_ZSTD_SERIAL;
@@ -1230,7 +1249,18 @@ static void plan_enqueue(zgpu_plan &P, uint8_t *out, hipStream_t s) {
     uint32_t *live = nullptr;
     if (wrote_direct && le && std::atoi(le) != 0)
       live = (uint32_t *)P.grow(P.live_list, ((size_t)ni + 1) * 4);
-    HIPCHK(launch_scatter(items, P.d_geom, P.d_status, P.scatter, out, ni, P.scatter_mode, P.scatter_units, s, live));
+    // both switches are read per launch (tests and A/B runs flip them in one process)
+    const char *pe = std::getenv("ZGPU_TILED_PERSIST");
+    const bool persist = P.tiled_p && (!pe || std::atoi(pe) != 0) && ((uintptr_t)out & 15) == 0;
+    if (persist) {
+      const char *ge = std::getenv("ZGPU_TILED_GRID");
+      const uint32_t cap = ge ? (uint32_t)std::strtoul(ge, nullptr, 10) : 0;
+      HIPCHK(launch_scatter_tiled_p(items, P.d_geom, P.d_status, P.d_origin, P.scatter, P.tiled_q, out, ni, cap, s));
+      P.last_path = ZGPU_SCATTER_TILED_PERSISTENT;
+    } else {
+      HIPCHK(launch_scatter(items, P.d_geom, P.d_status, P.scatter, out, ni, P.scatter_mode, P.scatter_units, s, live));
+      P.last_path = P.scatter_mode;
+    }
   }
 }
 
@@ -2057,6 +2087,8 @@ void zgpu_plan_destroy(zgpu_plan *P) {
   { std::lock_guard<std::mutex> lk(P->mu); }  // no execute of it still running on another thread
   delete P;
 }
+
+uint32_t zgpu_plan_scatter_path(const zgpu_plan *P) { return P ? P->last_path : ZGPU_SCATTER_GENERIC; }
 
 uint64_t zgpu_plan_algorithmic_bytes(const zgpu_plan *P) { return P ? P->alg_bytes_static + P->last_enc_bytes : 0; }
 
