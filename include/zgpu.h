@@ -130,9 +130,20 @@ const char *zgpu_version(void);
  *                Supported: transpose, bytes, sharding_indexed (nested to any depth, with codecs
  *                around the inner shardings and bytes->bytes codecs after any of them),
  *                crc32c (+numcodecs.crc32c), numcodecs.adler32 (location start, the default, or
- *                end), numcodecs.fletcher32, gzip, numcodecs.zlib, zstd, numcodecs.shuffle, blosc
- *                (blosclz, lz4, lz4hc, zlib, snappy, zstd; shuffle / bitshuffle). Others ->
- *                ZGPU_UNSUPPORTED.
+ *                end), numcodecs.fletcher32, gzip, numcodecs.zlib, numcodecs.bz2 (decode only),
+ *                zstd, numcodecs.shuffle, blosc (blosclz, lz4, lz4hc, zlib, snappy, zstd; shuffle /
+ *                bitshuffle). Others -> ZGPU_UNSUPPORTED.
+ *                numcodecs.bz2 ({"level": 0..9}, required, no other field) reads the first bzip2
+ *                stream of a chunk and ignores what follows it; the block CRCs and the combined
+ *                CRC are checked whatever validate_checksums says, and a truncated, malformed or
+ *                empty stream is ZGPU_CORRUPT_STREAM. Two deviations from libbz2: a block with the
+ *                "randomised" bit (written by bzip2 0.9.0 and older only) is ZGPU_CORRUPT_STREAM,
+ *                and a chunk whose stream holds more than 32 + slot bytes / 32768 block magics is
+ *                ZGPU_DECODED_SIZE_MISMATCH with an unknown length, like any stream that outgrows
+ *                its slot (libbz2 starts a new block every 99,981 symbols or more, so a stream
+ *                of so many blocks that fits its chunk is hand-made). The stage's scratch is
+ *                6.25 x the decoded bytes per chunk; ZGPU_BZ2_SCRATCH_MB (default 8192) bounds it,
+ *                and a larger batch is decoded in rounds.
  *  data_type   : Zarr V3 data type name ("float32", "uint16", ...); fixed-size types only.
  *  fill        : native-endian fill value bytes (FillValue::as_ne_bytes), fill_len == dtype size.
  *  validate_checksums : CodecOptions::validate_checksums (zarrs default true, options.rs:24-33).
@@ -320,7 +331,12 @@ void zgpu_group_destroy(zgpu_group *group);
                                     the selection (each decoded, or filled when empty)                 */
 #define ZGPU_CTR_ZSTD_LATENCY 6  /* zstd items finished by the window executor's latency mode (a subset
                                     of ZGPU_CTR_ZSTD_PARALLEL: small batches, one workgroup per window) */
-#define ZGPU_N_COUNTERS 7
+#define ZGPU_CTR_BZ2_BLOCKS 7    /* bzip2 blocks decoded by the numcodecs.bz2 stage (each one is a unit of
+                                    parallel work, whichever stream it came from)                      */
+#define ZGPU_CTR_BZ2_ROUNDS 8    /* rounds the numcodecs.bz2 stage ran: 1 per execution whose scratch fits
+                                    ZGPU_BZ2_SCRATCH_MB, more when the batch is cut; a whole-shard bz2
+                                    stage adds the rounds of every run of its slot regrowing           */
+#define ZGPU_N_COUNTERS 9
 uint32_t zgpu_plan_counters(const zgpu_plan *plan, uint64_t *out, uint32_t n);
 uint32_t zgpu_last_counters(uint64_t *out, uint32_t n);
 
@@ -431,7 +447,9 @@ int zgpu_encode_batch(zgpu_chain *chain, uint32_t ndim, const uint64_t *chunk_sh
  * blosclz, lz4 / lz4hc, snappy, zlib or zstd streams after a byte shuffle / bitshuffle (frames any
  * c-blosc 1.x decoder reads, not byte-identical to c-blosc's).
  * enc_lens[n] receives each chunk's encoded length; descs[i].dst_cap must be >=
- * zgpu_chain_encoded_bound. zgpu_chain_encoded_bound: the fixed size, or the worst case
+ * zgpu_chain_encoded_bound. numcodecs.bz2 has no encoder on the GPU: a chain with it returns
+ * ZGPU_UNSUPPORTED here, while zgpu_chain_encoded_bound still gives Bz2Codec's bound for it
+ * (bz2_codec.rs: size + size / 8 + 1024). zgpu_chain_encoded_bound: the fixed size, or the worst case
  * (gzip_codec.rs:122-136, zlib_codec.rs encoded_representation, zstd_codec.rs:132-147; a shard: every inner chunk at its bound + index),
  * -1 if unbounded.
  */

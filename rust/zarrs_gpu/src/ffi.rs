@@ -54,7 +54,9 @@ pub struct zgpu_group {
 pub const ZGPU_CTR_ITEMS: usize = 5;
 /// zgpu_last_counters index: zstd items finished by the window executor's latency mode.
 pub const ZGPU_CTR_ZSTD_LATENCY: usize = 6;
-pub const ZGPU_N_COUNTERS: usize = 7;
+pub const ZGPU_CTR_BZ2_BLOCKS: usize = 7;
+pub const ZGPU_CTR_BZ2_ROUNDS: usize = 8;
+pub const ZGPU_N_COUNTERS: usize = 9;
 
 /// zgpu_encode_desc: one chunk of a device-resident array encoded into `dst`.
 #[repr(C)]

@@ -48,8 +48,8 @@ EXPORTS = [
 ]
 SCATTER_ROWS, SCATTER_TILED, SCATTER_GENERIC, SCATTER_TILED_PERSISTENT = range(4)  # zgpu_plan_scatter_path
 CTR_ENC_BYTES, CTR_ZSTD_SERIAL, CTR_ZSTD_PARALLEL, CTR_BLOSC_RERUN, CTR_BLOSC_BLOCKS, CTR_ITEMS, \
-    CTR_ZSTD_LATENCY = range(7)
-N_COUNTERS = 7
+    CTR_ZSTD_LATENCY, CTR_BZ2_BLOCKS, CTR_BZ2_ROUNDS = range(9)
+N_COUNTERS = 9
 
 
 class ChunkDesc(C.Structure):
@@ -210,7 +210,7 @@ def last_counters() -> dict:
     buf = (C.c_uint64 * N_COUNTERS)()
     load().zgpu_last_counters(buf, N_COUNTERS)
     return {"enc_bytes": buf[0], "zstd_serial": buf[1], "zstd_parallel": buf[2], "blosc_rerun": buf[3],
-            "blosc_blocks": buf[4], "zstd_latency": buf[6]}
+            "blosc_blocks": buf[4], "zstd_latency": buf[6], "bz2_blocks": buf[7], "bz2_rounds": buf[8]}
 
 
 def last_size_mismatch():

@@ -1,8 +1,8 @@
 // Codec chain parsing (see chain.hpp). Reference: codec_chain.rs:192-229 (from_metadata: exactly one
 // array->bytes codec, error otherwise), zarrs_codec/src/lib.rs:372-449 (name -> codec lookup), and the
 // per-codec configurations in zarrs_metadata_ext/src/codec/registered/{transpose,bytes,sharding,
-// crc32c,gzip,zstd,shuffle}.rs, zarrs_metadata_ext/src/codec/numcodecs/{zlib,adler32,fletcher32}.rs
-// (created by zarrs/src/array/codec/bytes_to_bytes/{zlib,adler32,fletcher32}.rs).
+// crc32c,gzip,zstd,shuffle}.rs, zarrs_metadata_ext/src/codec/numcodecs/{zlib,adler32,fletcher32,bz2}.rs
+// (created by zarrs/src/array/codec/bytes_to_bytes/{zlib,adler32,fletcher32,bz2}.rs).
 #include "chain.hpp"
 
 #include <cstring>
@@ -39,7 +39,7 @@ static bool zarrs_knows(const std::string &n) {
   static const char *names[] = {
       "bitround", "numcodecs.bitround", "cast_value", "numcodecs.fixedscaleoffset", "reshape", "zarrs.squeeze",
       "packbits", "numcodecs.pcodec", "zfp", "zarrs.zfp", "numcodecs.zfpy", "zarrs.vlen", "zarrs.vlen_v2",
-      "vlen-bytes", "vlen-utf8", "vlen-array", "zarrs.optional", "numcodecs.bz2", "zarrs.gdeflate"};
+      "vlen-bytes", "vlen-utf8", "vlen-array", "zarrs.optional", "zarrs.gdeflate"};
   for (const char *k : names)
     if (n == k) return true;
   return n.rfind("https://codec.zarrs.dev/", 0) == 0;
@@ -114,6 +114,17 @@ static Role create_codec(Codec &k, const Json *cfg, const std::string &dt, uint3
     const Json *l = cfg_get("level");
     if (!l || l->kind != Json::Num || !l->is_int || l->i < 0 || l->i > 9)
       throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.zlib: level must be an integer 0..9"};
+    k.level = (int)l->i;
+  } else if (k.name == "numcodecs.bz2" || k.name == "https://codec.zarrs.dev/bytes_to_bytes/bz2") {
+    // Bz2CodecConfigurationV1 (bz2.rs): level 0..9, required; deny_unknown_fields. Decode reads the block
+    // size from the stream's own header digit
+    k.kind = CodecKind::Bz2;
+    if (!cfg || cfg->kind != Json::Obj) throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.bz2: missing configuration"};
+    for (const auto &kv : cfg->obj)
+      if (kv.first != "level") throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.bz2: unknown field '" + kv.first + "'"};
+    const Json *l = cfg_get("level");
+    if (!l || l->kind != Json::Num || !l->is_int || l->i < 0 || l->i > 9)
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.bz2: level must be an integer 0..9"};
     k.level = (int)l->i;
   } else if (k.name == "numcodecs.adler32") {
     // Adler32CodecConfigurationV1 (adler32.rs:47-59): location "start" (the default, unlike crc32c) / "end"
@@ -252,6 +263,9 @@ uint64_t zlib_bound(uint64_t n) { return n + (n >> 12) + (n >> 14) + (n >> 25) +
 // 3-byte block header per 1000 bytes
 uint64_t zstd_bound(uint64_t n) { return n + 4 + 14 + 4 + 3 * ((n + 999) / 1000); }
 
+// Bz2Codec::encoded_representation (bz2/bz2_codec.rs)
+uint64_t bz2_bound(uint64_t n) { return n + n / 8 + 1024; }
+
 int64_t chain_encoded_bound(const Chain &c, uint64_t nelem) {
   if (c.a2b.kind != CodecKind::Bytes) return -1;
   uint64_t n = nelem * c.es;
@@ -260,6 +274,7 @@ int64_t chain_encoded_bound(const Chain &c, uint64_t nelem) {
     else if (k.kind == CodecKind::Gzip) n = gzip_bound(n);
     else if (k.kind == CodecKind::Zlib) n = zlib_bound(n);
     else if (k.kind == CodecKind::Zstd) n = zstd_bound(n);
+    else if (k.kind == CodecKind::Bz2) n = bz2_bound(n);
     else if (k.kind == CodecKind::Blosc) n += 16;  // BLOSC_MAX_OVERHEAD (blosc_via_blosc_src.rs:80)
     else if (k.kind != CodecKind::Shuffle) return -1;
   }

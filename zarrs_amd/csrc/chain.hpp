@@ -12,7 +12,7 @@
 
 namespace zgpu {
 
-enum class CodecKind { Transpose, Bytes, Sharding, Crc32c, Gzip, Zstd, Shuffle, Blosc, Zlib, Adler32, Fletcher32 };
+enum class CodecKind { Transpose, Bytes, Sharding, Crc32c, Gzip, Zstd, Shuffle, Blosc, Zlib, Adler32, Fletcher32, Bz2 };
 
 struct Chain;
 
@@ -22,7 +22,7 @@ struct Codec {
   std::vector<uint32_t> order;        // transpose
   bool big_endian = false;            // bytes
   bool at_start = false;              // crc32c / adler32 location, sharding index_location
-  int level = 0;                      // gzip / zstd / zlib
+  int level = 0;                      // gzip / zstd / zlib / bz2
   bool checksum = false;              // zstd
   uint32_t elementsize = 4;           // shuffle; blosc typesize
   std::string cname;                  // blosc compressor (decode reads the compressor from the header)
@@ -64,10 +64,12 @@ int64_t chain_fixed_encoded_size(const Chain &c, uint64_t nelem);
 // Upper bound of one chunk's encoded size for an array->bytes `bytes` chain (BytesRepresentation::
 // BoundedSize): crc32c / adler32 / fletcher32 +4, gzip as GzipCodec::encoded_representation
 // (gzip_codec.rs:122-136, zlib's deflateBound), zlib as ZlibCodec's (zlib/zlib_codec.rs), zstd as
-// ZstdCodec's (zstd_codec.rs:132-147); -1 if unbounded.
+// ZstdCodec's (zstd_codec.rs:132-147), bz2 as Bz2Codec's (bz2_codec.rs: size + size / 8 + 1024); -1 if
+// unbounded.
 int64_t chain_encoded_bound(const Chain &c, uint64_t nelem);
 uint64_t gzip_bound(uint64_t n);
 uint64_t zlib_bound(uint64_t n);
 uint64_t zstd_bound(uint64_t n);
+uint64_t bz2_bound(uint64_t n);
 
 }  // namespace zgpu

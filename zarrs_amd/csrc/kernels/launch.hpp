@@ -353,6 +353,23 @@ hipError_t launch_adler32_check(const ZgItem *subs, uint32_t *sub_status, const 
 // after the stream are ignored.
 hipError_t launch_zlib_items(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst, uint64_t slot_bytes,
                              uint32_t *order, uint32_t *seg_scr, hipStream_t s);
+// numcodecs.bz2 stage of a plan (bz2_codec.rs; bzip2's BzDecoder + read_to_end): every live item's
+// first stream decoded into its dst slot, block-parallel (kernels/bz2.hip). The block CRCs and the
+// combined CRC are always checked (a mismatch is CORRUPT_STREAM); bytes after the stream are ignored.
+// The scratch holds round_items items of item_bytes = bz2_item_scratch_bytes(slot_bytes, cap, tt_cap)
+// each (block records, the BWT vector, the bytes before RLE1); larger batches run in rounds.
+struct Bz2Scratch {
+  uint8_t *base;
+  uint64_t item_bytes, tt_cap;
+  uint32_t cap;          // candidate / block records per item
+  uint32_t round_items;  // items per round (cap x round_items stays below 2^30 blocks per launch)
+  unsigned long long *blocks;  // blocks decoded (ctl counter; nullable)
+  uint32_t *lists;  // bz2_list_bytes(round_items, cap): the round's candidate and real-block work lists
+};
+inline uint64_t bz2_list_bytes(uint32_t round_items, uint32_t cap) { return 16 + 2ull * round_items * cap * 8; }
+uint64_t bz2_item_scratch_bytes(uint64_t slot_bytes, uint32_t &cap, uint64_t &tt_cap);
+hipError_t launch_bz2(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst, uint64_t slot_bytes,
+                      const Bz2Scratch &S, hipStream_t s);
 hipError_t launch_blosc_layout(const BlInfo *info, uint32_t n_items, uint64_t *bases, const BlCaps &caps,
                                const BlDecode &D, hipStream_t s);
 hipError_t launch_blosc_info(const ZgItem *items, uint32_t *status, uint32_t n_items, uint64_t slot_bytes,

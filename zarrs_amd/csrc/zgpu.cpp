@@ -40,7 +40,7 @@ namespace {
 thread_local std::string g_last_error;
 // device counters in the plan's control block (u64 each, cleared per execute)
 enum { CTR_ENC_BYTES = 0, CTR_ZSTD_SERIAL = 1, CTR_ZSTD_PARALLEL = 2, CTR_BLOSC_RERUN = 3, CTR_BLOSC_BLOCKS = 4,
-       CTR_ITEMS = 5, CTR_ZSTD_LATENCY = 6, CTR_N = 7 };  // CTR_ITEMS is host-side (the plan's leaf items)
+       CTR_ITEMS = 5, CTR_ZSTD_LATENCY = 6, CTR_BZ2_BLOCKS = 7, CTR_BZ2_ROUNDS = 8, CTR_N = 9 };  // CTR_ITEMS and CTR_BZ2_ROUNDS are host-side
 // internal ctl slots (not reported): a cached blosc layout was outgrown (the execution is re-run)
 enum { CTR_BLOSC_OVF = 31, CTR_SCRATCH = 30, CTR_ZSTD_NSER = 29, CTR_ZSTD_MAXBLK = 28 };  // not reported (device-side flags / sinks)
 thread_local uint64_t g_last_counters[CTR_N];
@@ -297,7 +297,7 @@ struct zgpu_chain {
 // ------------------------------------------------------------------------------------------------
 // Plan
 // ------------------------------------------------------------------------------------------------
-enum StageKind { ST_CRC32C, ST_GZIP, ST_ZSTD, ST_UNSHUFFLE, ST_BLOSC, ST_ADLER32, ST_FLETCHER32, ST_ZLIB };
+enum StageKind { ST_CRC32C, ST_GZIP, ST_ZSTD, ST_UNSHUFFLE, ST_BLOSC, ST_ADLER32, ST_FLETCHER32, ST_ZLIB, ST_BZ2 };
 // the checksum stages strip 4 bytes in place; every other stage materialises its output in a slot pool
 static bool strips_only(StageKind k) { return k == ST_CRC32C || k == ST_ADLER32 || k == ST_FLETCHER32; }
 static StageKind checksum_stage(CodecKind k) {
@@ -442,6 +442,8 @@ struct zgpu_plan {
   uint32_t *d_zser = nullptr;
   uint32_t *d_order = nullptr;  // gzip stage: LPT dispatch order of the items
   uint32_t *d_gz_seg = nullptr;  // gzip stage: symbol-record scratch of the segmented decode
+  uint64_t bz_rounds = 0;  // bz2 stage: rounds the last enqueue launched (ZGPU_CTR_BZ2_ROUNDS)
+  Bz2Scratch bz{};  // bz2 stage: block records, BWT vectors and pre-RLE1 bytes of one round of items
   bool no_scatter = false;  // a whole-shard predecode plan: its bytes->bytes stages only (decode_general)
 
   ~zgpu_plan() {
@@ -458,7 +460,7 @@ struct zgpu_plan {
     void *bufs[] = {d_items, d_items_init, d_geom, d_shards, d_index, d_shard_status, d_mids, d_mids_init,
                     d_mid_status, d_shard_status2, d_mid_shards, d_index2, d_bl_need,
                     d_pool[0], d_pool[1], zs.blks, zs.nblk, zs.mode, zs.lit, zs.seq, d_ctl,
-                    d_enc_stage, d_zser, d_order, d_gz_seg, zs.lit_rec, zs.ext, zs.ext_cnt, zs.norm, d_origin};
+                    d_enc_stage, d_zser, d_order, d_gz_seg, bz.base, zs.lit_rec, zs.ext, zs.ext_cnt, zs.norm, d_origin};
     for (void *b : bufs) ctx->dev_free(b);
     if (zside) {
       (void)hipStreamSynchronize(zside);
@@ -554,6 +556,7 @@ static void build_leaf_stages(zgpu_plan &P, const Chain &leaf, uint64_t nelem) {
     if (out_size < 0) throw ChainError{ZGPU_UNSUPPORTED, "a compressor nested inside another variable-size codec"};
     s.kind = k.kind == CodecKind::Gzip    ? ST_GZIP
              : k.kind == CodecKind::Zlib  ? ST_ZLIB
+             : k.kind == CodecKind::Bz2   ? ST_BZ2
              : k.kind == CodecKind::Zstd  ? ST_ZSTD
              : k.kind == CodecKind::Blosc ? ST_BLOSC
                                           : ST_UNSHUFFLE;
@@ -961,6 +964,20 @@ static void plan_upload(zgpu_plan &P, hipStream_t us) {
         P.d_order = (uint32_t *)C.dev_alloc(ni * 4);
         if (const uint64_t b = gzip_seg_scratch_bytes((uint32_t)ni)) P.d_gz_seg = (uint32_t *)C.dev_alloc(b);
       }
+      if (s.kind == ST_BZ2 && !P.bz.base) {
+        // 5 x slot_bytes of BWT vector (+ 1.25 x of bytes before RLE1, + block records) per item: a batch
+        // whose scratch passes the budget (ZGPU_BZ2_SCRATCH_MB, read per plan; default 8192) runs in rounds
+        P.bz.item_bytes = bz2_item_scratch_bytes(P.slot_bytes, P.bz.cap, P.bz.tt_cap);
+        const char *e = std::getenv("ZGPU_BZ2_SCRATCH_MB");
+        const uint64_t mb = e ? std::strtoull(e, nullptr, 10) : 0;
+        const uint64_t budget = (mb ? mb : 8192) << 20;
+        uint64_t per_round = std::max<uint64_t>(1, budget / P.bz.item_bytes);
+        per_round = std::min<uint64_t>(per_round, std::max<uint64_t>(1, (1u << 30) / P.bz.cap));
+        P.bz.round_items = (uint32_t)std::min<uint64_t>(per_round, ni);
+        const uint64_t items_bytes = P.bz.round_items * P.bz.item_bytes;  // a multiple of 256
+        P.bz.base = (uint8_t *)C.dev_alloc(items_bytes + bz2_list_bytes(P.bz.round_items, P.bz.cap));
+        P.bz.lists = (uint32_t *)(P.bz.base + items_bytes);
+      }
       if (s.kind == ST_ZSTD && !P.zs.blks) {
         uint64_t blk_bytes;
         zstd_scratch_layout(P.slot_bytes, P.zs.blk_cap, blk_bytes, P.zs.lit_stride, P.zs.seq_cap);
@@ -1144,6 +1161,7 @@ static void blosc_stage(zgpu_plan &P, const Stage &st, uint8_t *out, hipStream_t
 static void plan_enqueue(zgpu_plan &P, uint8_t *out, hipStream_t s) {
   const uint32_t ni = (uint32_t)P.items.size();
   P.last_out = out;
+  P.bz_rounds = 0;
   HIPCHK(hipMemsetAsync(P.d_ctl, 0, P.ctl_bytes, s));
   if (!ni) return;
   P.zs.launch_serial = P.zstd_serial_off ? 0u : 1u;
@@ -1187,6 +1205,11 @@ static void plan_enqueue(zgpu_plan &P, uint8_t *out, hipStream_t s) {
       case ST_ZLIB:
         HIPCHK(launch_zlib_items(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.slot_bytes, P.d_order, P.d_gz_seg,
                                  s));
+        break;
+      case ST_BZ2:
+        P.bz.blocks = P.d_counter + CTR_BZ2_BLOCKS;
+        P.bz_rounds += (ni + P.bz.round_items - 1) / P.bz.round_items;
+        HIPCHK(launch_bz2(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.slot_bytes, P.bz, s));
         break;
       case ST_CRC32C:
         if (!st.at_start && si + 1 < P.stages.size() && P.stages[si + 1].kind == ST_GZIP && P.d_gz_seg) {
@@ -1321,6 +1344,7 @@ static int plan_statuses(zgpu_plan &P, int32_t *status, hipStream_t s) {
   }
   std::memcpy(P.last_counters, P.h_ctl, sizeof(P.last_counters));
   P.last_counters[CTR_ITEMS] = ni;
+  P.last_counters[CTR_BZ2_ROUNDS] = P.bz_rounds;
   for (int k = 0; k < CTR_N; k++) g_last_counters[k] += P.last_counters[k];
   const uint32_t *st = (const uint32_t *)(P.h_ctl + 256);
   P.last_enc_bytes = P.last_counters[CTR_ENC_BYTES];
@@ -1484,7 +1508,8 @@ static void run_sub(GeneralCall &G, const std::shared_ptr<Chain> &chain, const s
 // status): decoded by a stages-only plan whose slots hold the decoded shards. Compressors size the
 // slots from the streams (kernels/probe.hip); a gzip member longer than its ISIZE hint is re-run
 // with larger slots up to DEFLATE's 1032:1 bound, and so is a zlib stream, which carries no size:
-// its slots start at four times the encoded shard.
+// its slots start at four times the encoded shard. A bz2 stream carries no size either and has no
+// useful ratio bound (50 bytes decode to 45,899,000 zeros), so only the slot limit ends its regrowing.
 static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &items, std::vector<int32_t> &ist) {
   std::vector<uint32_t> todo;
   for (uint32_t i = 0; i < items.size(); i++)
@@ -1498,6 +1523,7 @@ static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &ite
     case CodecKind::Fletcher32: st.kind = checksum_stage(k.kind); st.at_start = k.at_start; break;
     case CodecKind::Gzip: st.kind = ST_GZIP; hint_kind = SIZE_HINT_GZIP; break;
     case CodecKind::Zlib: st.kind = ST_ZLIB; break;  // no size in the stream: the regrow loop below finds it
+    case CodecKind::Bz2: st.kind = ST_BZ2; break;    // likewise
     case CodecKind::Zstd: st.kind = ST_ZSTD; hint_kind = SIZE_HINT_ZSTD; break;
     case CodecKind::Blosc: st.kind = ST_BLOSC; hint_kind = SIZE_HINT_BLOSC; break;
     case CodecKind::Shuffle: st.kind = ST_UNSHUFFLE; st.elementsize = k.elementsize; break;
@@ -1506,7 +1532,7 @@ static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &ite
   uint64_t cap = 0;
   if (st.kind == ST_UNSHUFFLE) {
     for (uint32_t t : todo) cap = std::max(cap, items[t].len);
-  } else if (st.kind == ST_ZLIB) {
+  } else if (st.kind == ST_ZLIB || st.kind == ST_BZ2) {
     for (uint32_t t : todo) cap = std::max(cap, items[t].len * 4);  // a first guess; regrown 8x on a mismatch
   } else if (hint_kind != UINT32_MAX) {
     const uint32_t nt = (uint32_t)todo.size();
@@ -1579,16 +1605,20 @@ static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &ite
     }
   };
   std::vector<uint32_t> again;
+  auto bound_of = [&](uint32_t t) {
+    return st.kind == ST_BZ2 ? slot_limit : std::min(items[t].len * 1032 + 1024, slot_limit);
+  };
   for (size_t j = 0; j < todo.size(); j++) {
     const uint32_t t = todo[j];
-    const uint64_t bound = std::min(items[t].len * 1032 + 1024, slot_limit);
-    if (s[j] == ZGPU_DECODED_SIZE_MISMATCH && (st.kind == ST_GZIP || st.kind == ST_ZLIB) && cap < bound)
+    const uint64_t bound = bound_of(t);
+    if (s[j] == ZGPU_DECODED_SIZE_MISMATCH && (st.kind == ST_GZIP || st.kind == ST_ZLIB || st.kind == ST_BZ2) &&
+        cap < bound)
       again.push_back(t);
     else
       settle(t, s[j], res[j]);
   }
   for (uint32_t t : again) {
-    const uint64_t bound = std::min(items[t].len * 1032 + 1024, slot_limit);
+    const uint64_t bound = bound_of(t);
     for (uint64_t c = std::min(cap * 8, bound);; c = std::min(c * 8, bound)) {
       run({t}, c, s, res);
       if (!(s[0] == ZGPU_DECODED_SIZE_MISMATCH && c < bound)) {
@@ -3279,9 +3309,9 @@ static int encode_fixed(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t
 static bool chain_compresses(const Chain &c) {
   for (const Codec &k : c.b2b)
     if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib || k.kind == CodecKind::Zstd ||
-        k.kind == CodecKind::Blosc)
+        k.kind == CodecKind::Blosc || k.kind == CodecKind::Bz2)
       return true;
-  return false;  // (blosc is refused by encode_var: its encoder is not on the GPU)
+  return false;  // (bz2 is refused by encode_var: it has no encoder on the GPU)
 }
 
 // CodecChain::encode (codec_chain.rs:528-555) of a chain with a compressor, for n chunks whose origins
@@ -3317,6 +3347,8 @@ static int encode_var(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t *
       size = zstd_bound(size);
     } else if (k.kind == CodecKind::Blosc) {
       size += 16;
+    } else if (k.kind == CodecKind::Bz2) {
+      return set_err(ZGPU_UNSUPPORTED, "encode: numcodecs.bz2 is decode-only on the GPU");
     } else {
       return set_err(ZGPU_UNSUPPORTED, "encode: only transpose / bytes / numcodecs.shuffle (innermost, elementsize = "
                                        "data type size) / crc32c / adler32 / fletcher32 / gzip / zlib / zstd / blosc "
