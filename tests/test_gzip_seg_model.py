@@ -1,5 +1,5 @@
 """CPU check of the synchronisation logic of k_gzip's segmented symbol decode (tools/gzip_seg_model.py
-restates kernels/inflate.hip's ZG_INFLATE_SEG path): lanes decode stream regions from an early start,
+restates kernels/inflate.hip's segmented rounds): lanes decode stream regions from an early start,
 validate against their predecessor's exit, re-decode when out of sync; the records of the valid lanes,
 executed in order, must reproduce zlib's output exactly (dynamic, fixed and stored blocks; levels
 1/6/9; tight overlaps that force repairs and record caps that end rounds early)."""

@@ -1,4 +1,4 @@
-"""CPU model of k_gzip's segmented symbol decode (kernels/inflate.hip, ZG_INFLATE_SEG): the check of
+"""CPU model of k_gzip's segmented symbol decode (kernels/inflate.hip, "segmented rounds"): the check of
 its synchronisation logic against zlib, and the source of its sync statistics.
 
 A Huffman block is decoded in rounds. In a round starting at the true bit position r0, lane l owns

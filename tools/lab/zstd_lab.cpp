@@ -189,7 +189,7 @@ int main(int argc, char **argv) {
   int ncu = 256;
   CK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
   const int reps = getenv("LAB_REPS") ? atoi(getenv("LAB_REPS")) : 3;
-  uint8_t *lit_rec = nullptr;  // literal record slots (ZG_LIT_REC; LAB_NOREC=1: none)
+  uint8_t *lit_rec = nullptr;  // literal record slots (LAB_NOREC=1: none)
   {
     uint32_t wgs = 0;
     const uint64_t rb = zgpu::zstd_lit_rec_bytes(wgs);
@@ -209,19 +209,9 @@ int main(int argc, char **argv) {
                        Z.lit_stride, Z.seq_cap, 0u, (unsigned long long *)nullptr, (uint32_t *)nullptr,
                        (unsigned long long *)nullptr, (unsigned long long *)nullptr, Z.norm);
     CK(hipEventRecord(ev[1]));
-    const int seqm = getenv("LAB_SEQLG") ? atoi(getenv("LAB_SEQLG")) : 1;
-    if (seqm == 1) {  // the lane-group sequence decoder, as launch_zstd_pass
-      const uint64_t per_cu =
-          std::max<uint64_t>(1, (160u << 10) / ((sizeof(zgpu::ZDecLgSmem<ZG_SEQ_G>) + 1023) & ~size_t(1023)));
-      const uint32_t lg_grid =
-          (uint32_t)std::min<uint64_t>((recs + ZG_SEQ_G - 1) / ZG_SEQ_G, (uint64_t)ncu * per_cu);
-      hipLaunchKernelGGL(zgpu::k_zstd_blocks_lg<ZG_SEQ_G>, dim3(lg_grid), dim3(64), 0, 0, d_items, d_status, blks,
-                         Z.blk_cap, Z.nblk, Z.mode, (uint32_t)n, Z.seq, Z.seq_cap, (const unsigned long long *)nullptr);
-    } else {
-      hipLaunchKernelGGL(zgpu::k_zstd_blocks, dim3(bgrid), dim3(64), 0, 0, d_items, d_status, blks, Z.blk_cap,
-                         Z.nblk, Z.mode, (uint32_t)n, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap,
-                         (const unsigned long long *)nullptr, Z.norm);
-    }
+    hipLaunchKernelGGL(zgpu::k_zstd_blocks, dim3(bgrid), dim3(64), 0, 0, d_items, d_status, blks, Z.blk_cap, Z.nblk,
+                       Z.mode, (uint32_t)n, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, (const unsigned long long *)nullptr,
+                       Z.norm);
     CK(hipEventRecord(ev[2]));
     hipLaunchKernelGGL(zgpu::k_zstd_huf, dim3(grid), dim3(64), 0, 0, d_items, d_status, blks, Z.blk_cap, Z.nblk, Z.mode,
                        (uint32_t)n, Z.lit, Z.lit_stride, (const unsigned long long *)nullptr);

@@ -26,7 +26,10 @@
 //                    through an LDS window, recent output in an LDS ring. The one-wave kernels k_lz4,
 //                    k_blosclz, k_snappy and Lz32 are not reached by the default build (lz_list is always
 //                    allocated and ZG_LZM_G is 32): only -DZG_LZM_G=64 launches them, and the hand-built
-//                    frame tests (tests/test_gpu_blosc_frames.py) do not cover them
+//                    frame tests (tests/test_gpu_blosc_frames.py) do not cover them. They are still here
+//                    because deleting all three changes the code the compiler emits for k_snappym (its
+//                    interprocedural constant propagation then folds one more value there): that
+//                    needs a measurement of the snappy path with it
 //   zlib streams     k_gzip's DEFLATE decoder with the RFC 1950 wrapper (inflate.hip), then the
 //                    Adler-32 trailer check (k_adler32_check, crc.hip)
 //   k_blosc_finish   one workgroup per block: gathers the block's streams and unshuffles /
@@ -1084,6 +1087,27 @@ hipError_t launch_blosc_layout(const BlInfo *info, uint32_t n_items, uint64_t *b
   return hipGetLastError();
 }
 
+// One LZ kind's streams: the narrow and the wide list, then the decoder over each (two streams per
+// wave; one per wave for bitshuffled blocks). Without a list, or built with -DZG_LZM_G=64: the
+// one-wave kernel over every stream.
+template <auto Narrow, auto Wide, auto OneWave>
+static void launch_lz_kind(const BlDecode &D, uint32_t kind, hipStream_t s) {
+  if (D.lz_list && ZG_LZM_G < 64) {
+    uint32_t *wl = D.lz_list + D.n_sub + 1;  // the wide list
+    hipLaunchKernelGGL(k_lz_list, dim3(1), dim3(1024), 0, s, D.subs, D.sub_kind, D.sub_status, (uint32_t)D.n_sub,
+                       kind, 0u, D.lz_list);
+    hipLaunchKernelGGL(k_lz_list, dim3(1), dim3(1024), 0, s, D.subs, D.sub_kind, D.sub_status, (uint32_t)D.n_sub,
+                       kind, 1u, wl);
+    constexpr uint32_t NG = 64 / ZG_LZM_G;
+    hipLaunchKernelGGL(Narrow, dim3((uint32_t)((D.n_sub + NG - 1) / NG)), dim3(64), 0, s, D.subs, D.sub_status,
+                       D.lz_list, D.tmp, D.sub_slot);
+    hipLaunchKernelGGL(Wide, dim3((uint32_t)D.n_sub), dim3(64), 0, s, D.subs, D.sub_status, wl, D.tmp, D.sub_slot);
+  } else {
+    hipLaunchKernelGGL(OneWave, dim3((uint32_t)D.n_sub), dim3(64), 0, s, D.subs, D.sub_status, D.sub_kind,
+                       (uint32_t)D.n_sub, D.tmp, D.sub_slot);
+  }
+}
+
 hipError_t launch_blosc_decode(ZgItem *items, uint32_t *status, uint32_t n_items, const BlInfo *info,
                                const BlDecode &D, uint8_t *dst, uint64_t slot_bytes, hipStream_t s) {
   if (!n_items) return hipSuccess;
@@ -1096,56 +1120,14 @@ hipError_t launch_blosc_decode(ZgItem *items, uint32_t *status, uint32_t n_items
     hipError_t e = launch_zstd(D.subs, D.sub_status, (uint32_t)D.n_sub, D.tmp, D.sub_slot, D.zs, s);
     if (e != hipSuccess) return e;
   }
-  if (D.n_lz4 && D.lz_list && ZG_LZM_G < 64) {
-    uint32_t *wl = D.lz_list + D.n_sub + 1;  // the wide list
-    hipLaunchKernelGGL(k_lz_list, dim3(1), dim3(1024), 0, s, D.subs, D.sub_kind, D.sub_status, (uint32_t)D.n_sub,
-                       (uint32_t)BL_KIND_LZ4, 0u, D.lz_list);
-    hipLaunchKernelGGL(k_lz_list, dim3(1), dim3(1024), 0, s, D.subs, D.sub_kind, D.sub_status, (uint32_t)D.n_sub,
-                       (uint32_t)BL_KIND_LZ4, 1u, wl);
-    constexpr uint32_t NG = 64 / ZG_LZM_G;
-    hipLaunchKernelGGL(k_lz4m<ZG_LZM_G>, dim3((uint32_t)((D.n_sub + NG - 1) / NG)), dim3(64), 0, s, D.subs,
-                       D.sub_status, D.lz_list, D.tmp, D.sub_slot);
-    hipLaunchKernelGGL(k_lz4m<64>, dim3((uint32_t)D.n_sub), dim3(64), 0, s, D.subs, D.sub_status, wl, D.tmp,
-                       D.sub_slot);
-  } else if (D.n_lz4) {
-    hipLaunchKernelGGL(k_lz4, dim3((uint32_t)D.n_sub), dim3(64), 0, s, D.subs, D.sub_status, D.sub_kind,
-                       (uint32_t)D.n_sub, D.tmp, D.sub_slot);
-  }
+  if (D.n_lz4) launch_lz_kind<k_lz4m<ZG_LZM_G>, k_lz4m<64>, k_lz4>(D, BL_KIND_LZ4, s);
   if (D.n_zlib) {
     hipError_t e = launch_zlib_streams(D.subs, D.sub_status, D.sub_kind, (uint32_t)D.n_sub, D.tmp, D.sub_slot, D.zaux, D.zseg, s);
     if (e == hipSuccess) e = launch_adler32_check(D.subs, D.sub_status, D.sub_kind, (uint32_t)D.n_sub, D.zaux, s);
     if (e != hipSuccess) return e;
   }
-  if (D.n_snappy && D.lz_list && ZG_LZM_G < 64) {
-    uint32_t *wl = D.lz_list + D.n_sub + 1;  // the wide list
-    hipLaunchKernelGGL(k_lz_list, dim3(1), dim3(1024), 0, s, D.subs, D.sub_kind, D.sub_status, (uint32_t)D.n_sub,
-                       (uint32_t)BL_KIND_SNAPPY, 0u, D.lz_list);
-    hipLaunchKernelGGL(k_lz_list, dim3(1), dim3(1024), 0, s, D.subs, D.sub_kind, D.sub_status, (uint32_t)D.n_sub,
-                       (uint32_t)BL_KIND_SNAPPY, 1u, wl);
-    constexpr uint32_t NG = 64 / ZG_LZM_G;
-    hipLaunchKernelGGL(k_snappym<ZG_LZM_G>, dim3((uint32_t)((D.n_sub + NG - 1) / NG)), dim3(64), 0, s, D.subs,
-                       D.sub_status, D.lz_list, D.tmp, D.sub_slot);
-    hipLaunchKernelGGL(k_snappym<64>, dim3((uint32_t)D.n_sub), dim3(64), 0, s, D.subs, D.sub_status, wl, D.tmp,
-                       D.sub_slot);
-  } else if (D.n_snappy) {
-    hipLaunchKernelGGL(k_snappy, dim3((uint32_t)D.n_sub), dim3(64), 0, s, D.subs, D.sub_status, D.sub_kind,
-                       (uint32_t)D.n_sub, D.tmp, D.sub_slot);
-  }
-  if (D.n_blosclz && D.lz_list && ZG_LZM_G < 64) {
-    uint32_t *wl = D.lz_list + D.n_sub + 1;  // the wide list
-    hipLaunchKernelGGL(k_lz_list, dim3(1), dim3(1024), 0, s, D.subs, D.sub_kind, D.sub_status, (uint32_t)D.n_sub,
-                       (uint32_t)BL_KIND_BLOSCLZ, 0u, D.lz_list);
-    hipLaunchKernelGGL(k_lz_list, dim3(1), dim3(1024), 0, s, D.subs, D.sub_kind, D.sub_status, (uint32_t)D.n_sub,
-                       (uint32_t)BL_KIND_BLOSCLZ, 1u, wl);
-    constexpr uint32_t NG = 64 / ZG_LZM_G;
-    hipLaunchKernelGGL(k_blosclzm<ZG_LZM_G>, dim3((uint32_t)((D.n_sub + NG - 1) / NG)), dim3(64), 0, s, D.subs,
-                       D.sub_status, D.lz_list, D.tmp, D.sub_slot);
-    hipLaunchKernelGGL(k_blosclzm<64>, dim3((uint32_t)D.n_sub), dim3(64), 0, s, D.subs, D.sub_status, wl, D.tmp,
-                       D.sub_slot);
-  } else if (D.n_blosclz) {
-    hipLaunchKernelGGL(k_blosclz, dim3((uint32_t)D.n_sub), dim3(64), 0, s, D.subs, D.sub_status, D.sub_kind,
-                       (uint32_t)D.n_sub, D.tmp, D.sub_slot);
-  }
+  if (D.n_snappy) launch_lz_kind<k_snappym<ZG_LZM_G>, k_snappym<64>, k_snappy>(D, BL_KIND_SNAPPY, s);
+  if (D.n_blosclz) launch_lz_kind<k_blosclzm<ZG_LZM_G>, k_blosclzm<64>, k_blosclz>(D, BL_KIND_BLOSCLZ, s);
   if (D.n_blk)
     hipLaunchKernelGGL(k_blosc_finish, dim3((uint32_t)D.n_blk), dim3(256), 0, s, D.blocks, D.subs, D.sub_status,
                        D.sub_kind, status, dst, slot_bytes, items, D.dout, D.geom, D.sc,

@@ -104,24 +104,6 @@ constexpr int LROOT = ZG_INFLATE_LROOT, DROOT = 8;
 // root is 852 entries in all (340 in subtables); distance subtables are sized for real data (C3
 // chunks need at most 16 entries with an 8-bit root): prefixes past the space take the slow path.
 constexpr int LSUB = ZG_INFLATE_LSUB, DSUB = ZG_INFLATE_DSUB;
-#ifndef ZG_INFLATE_SELECT
-#define ZG_INFLATE_SELECT 1  // lane symbol decode by selects instead of divergent branches
-#endif
-#ifndef ZG_INFLATE_XDEP
-#define ZG_INFLATE_XDEP 1  // matches resolve by exact dependencies (0: first-pending frontier)
-#endif
-#ifndef ZG_INFLATE_RANGE
-#define ZG_INFLATE_RANGE 1  // a match's readiness: pending mask vs the index range of its source
-#endif
-#ifndef ZG_INFLATE_XW
-#define ZG_INFLATE_XW 8  // > 0: in-ring matches up to this many bytes copy through aligned ring words
-#endif
-#ifndef ZG_INFLATE_BW
-#define ZG_INFLATE_BW 1  // window words by plain readlanes when they lie in one register window
-#endif
-#ifndef ZG_INFLATE_PJ
-#define ZG_INFLATE_PJ 1  // chain a window's symbols by pointer jumping (0: scalar walk)
-#endif
 #ifndef ZG_INFLATE_PJL
 #define ZG_INFLATE_PJL 2  // pointer-jumping doublings: a window chains up to 2^(PJL+1) symbols
 #endif
@@ -288,7 +270,6 @@ __device__ __forceinline__ void bits_words(Bits &B, uint32_t w, uint32_t &W0, ui
                                            uint32_t &W3, uint32_t &W4) {
   bits_advance_to(B, w);
   const uint32_t k = w - B.wcur;
-#if ZG_INFLATE_BW
   if (k <= 59) {  // all five in the first window (the common case): five plain readlanes
     W0 = U(__builtin_amdgcn_readlane(B.win0, (int)k));
     W1 = U(__builtin_amdgcn_readlane(B.win0, (int)k + 1));
@@ -297,7 +278,6 @@ __device__ __forceinline__ void bits_words(Bits &B, uint32_t w, uint32_t &W0, ui
     W4 = U(__builtin_amdgcn_readlane(B.win0, (int)k + 4));
     return;
   }
-#endif
   W0 = win_word(B, k);
   W1 = win_word(B, k + 1);
   W2 = win_word(B, k + 2);
@@ -546,7 +526,6 @@ __device__ __forceinline__ void lane_symbol(const Smem &S, uint32_t Vlo, uint32_
   uint32_t D = S.dtab[(Vlo >> s1) & ((1u << DROOT) - 1)];
   if (D & F_SUBT) D = S.dtab[(D >> 16) + ((uint32_t)(V >> (s1 + DROOT)) & ((1u << ((D >> 6) & 15)) - 1))];
   const uint32_t DL = D & 15, dx = (D >> 6) & 15, s2 = s1 + DL;
-#if ZG_INFLATE_SELECT
   // every kind computed, then selected (no divergent branches)
   const uint32_t len = (E >> 16) + ((Vlo >> L) & ((1u << lx) - 1));
   const uint32_t dist = (D >> 16) + ((uint32_t)(V >> s2) & ((1u << dx) - 1));
@@ -554,22 +533,6 @@ __device__ __forceinline__ void lane_symbol(const Smem &S, uint32_t Vlo, uint32_
   const uint32_t i_oth = kind == K_EOB ? (L | F_EOB) : F_BAD;
   info = kind == K_LIT ? (L | (1u << 8)) : (kind == K_LEN ? i_len : i_oth);
   rec = kind == K_LIT ? (E >> 16) : (0x80000000u | (dist << 9) | len);
-#else
-  if (kind == K_LIT) {
-    info = L | (1u << 8);
-    rec = E >> 16;
-  } else if (kind == K_LEN) {
-    const uint32_t len = (E >> 16) + ((Vlo >> L) & ((1u << lx) - 1));
-    const uint32_t dist = (D >> 16) + ((uint32_t)(V >> s2) & ((1u << dx) - 1));
-    info = (s2 + dx) | (len << 8);
-    rec = 0x80000000u | (dist << 9) | len;
-    if (DL == 0) info = F_SLOW;  // distance code past the subtable space
-    else if (((D >> 4) & 3) != K_LEN) info = F_BAD;
-  } else {
-    info = kind == K_EOB ? (L | F_EOB) : F_BAD;
-    rec = 0;
-  }
-#endif
   if (L == 0) info = F_SLOW;  // literal/length code past the subtable space
 }
 
@@ -669,10 +632,6 @@ __device__ inline uint32_t wave_crc(const uint8_t *p, uint64_t n, const CrcTable
 // output array: row p >> lbs of the chunk, whose index splits over the row axes innermost first
 // (extent 2^sh[k] each, the outermost unbounded), at column p & (2^lbs - 1). 16-B pieces never
 // straddle a row (rows are multiples of 16 bytes on 16-B aligned addresses).
-#ifndef ZG_GZ_DIRECT_READS
-#define ZG_GZ_DIRECT_READS 0  // 1: a direct item lives only in the array (sources older than the ring read
-                              // back from its rows, no slot copy); 0: the slot is written too (A/B)
-#endif
 struct OutMap {
   uint8_t *slot;  // the item's slot: always written (sources older than the ring are read back from it)
   uint8_t *base;
@@ -685,37 +644,9 @@ struct OutMap {
     return base + (p & ((1ull << lbs) - 1)) + (uint64_t)(r & ((1u << sh) - 1u)) * o0 + (uint64_t)(r >> sh) * o1;
   }
   __device__ __forceinline__ const uint8_t *rd(uint64_t p) const {  // a source byte older than the ring
-    return (ZG_GZ_DIRECT_READS && (cfg >> 31) && p < want) ? at(p) : slot + p;
+    return slot + p;
   }
 };
-
-#if ZG_GZ_DIRECT_READS
-// The CRC of decoded bytes [0, n) of a direct item: wave_crc's lane segments, each run over its row pieces.
-__device__ inline uint32_t wave_crc_map(const OutMap &O, uint64_t n, const CrcTables &T, uint32_t poly) {
-  if (!(O.cfg >> 31) || n > O.want) return wave_crc(O.slot, n, T, poly);
-  const uint32_t l = (uint32_t)lane_id(), lbs = O.cfg & 255;
-  uint64_t seg = (n + 63) / 64;
-  seg = (seg + 15) & ~(uint64_t)15;
-  const uint64_t b0 = min<uint64_t>((uint64_t)l * seg, n), b1 = min<uint64_t>(b0 + seg, n);
-  uint32_t c = 0xFFFFFFFFu;
-  for (uint64_t q = b0; q < b1;) {
-    const uint64_t e = min<uint64_t>(b1, ((q >> lbs) + 1) << lbs);
-    c = crc_run(c, O.at(q), e - q, T);
-    q = e;
-  }
-  c = ~c;
-  uint64_t len = b1 - b0;
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t c2 = __shfl_down(c, off, 64);
-    const uint64_t l2 = __shfl_down(len, off, 64);
-    if (l % (2 * off) == 0 && l + off < 64) {
-      c = crc_combine(c, c2, l2, T.x2n, poly);
-      len += l2;
-    }
-  }
-  return U(__shfl(c, 0, 64));
-}
-#endif
 
 __device__ __forceinline__ void flush(const Smem &S, const OutMap &O, uint64_t cap, uint64_t from, uint64_t to) {
   const uint64_t a = from & ~(uint64_t)15, b = (to + 15) & ~(uint64_t)15;
@@ -723,21 +654,18 @@ __device__ __forceinline__ void flush(const Smem &S, const OutMap &O, uint64_t c
     if (p + 16 <= cap) {
       const uint4 v = *(const uint4 *)&S.ring[p & RMASK];
       const bool d = (O.cfg >> 31) && p < O.want;  // want is a multiple of 16
-      if (!ZG_GZ_DIRECT_READS || !d) *(uint4 *)(O.slot + p) = v;
+      *(uint4 *)(O.slot + p) = v;
       if (d) *(uint4 *)O.at(p) = v;
     } else {
       for (uint64_t q = p; q < cap && q < p + 16; q++) {
         const bool d = (O.cfg >> 31) && q < O.want;
-        if (!ZG_GZ_DIRECT_READS || !d) O.slot[q] = S.ring[q & RMASK];
+        O.slot[q] = S.ring[q & RMASK];
         if (d) *O.at(q) = S.ring[q & RMASK];
       }
     }
   }
 }
 
-#ifndef ZG_INFLATE_SEG
-#define ZG_INFLATE_SEG 1  // Huffman blocks: every lane decodes a region of the stream serially (k_gzip's seg path)
-#endif
 #ifndef ZG_INFLATE_SEGB
 #define ZG_INFLATE_SEGB 512  // bits of the stream per lane region
 #endif
@@ -746,15 +674,6 @@ __device__ __forceinline__ void flush(const Smem &S, const OutMap &O, uint64_t c
 #endif
 #ifndef ZG_INFLATE_SEGCAP
 #define ZG_INFLATE_SEGCAP 96  // symbol records per lane region (a fuller region ends the round there)
-#endif
-#ifndef ZG_INFLATE_PCL
-#define ZG_INFLATE_PCL 1  // dynamic-header code lengths decoded lane-parallel (pointer-jumped windows)
-#endif
-#ifndef ZG_INFLATE_PIV
-#define ZG_INFLATE_PIV 1  // exec_batch: match source ranges by a two-level pivot search (no LDS search chain)
-#endif
-#ifndef ZG_INFLATE_XFETCH
-#define ZG_INFLATE_XFETCH 1  // executor batches: region lookup by ballots + records loaded a batch ahead
 #endif
 #ifndef ZG_INFLATE_MAXREP
 #define ZG_INFLATE_MAXREP 8  // out-of-sync lanes re-decoded per round from their predecessor's exit
@@ -878,7 +797,6 @@ __device__ __forceinline__ bool exec_batch(SM &S, const OutMap &O, uint64_t cap,
   if (__ballot(is_match && md > mypos)) return false;  // distance too far back
   // sources older than the ring are read back from the flushed output
   if (__ballot(is_match && msrc + RING < batch_end)) __threadfence_block();
-#if ZG_INFLATE_XDEP
   // Matches resolve in rounds by exact dependencies: a match waits only while the last symbol
   // starting before the end of its source (found once per batch by a binary search over the
   // symbols' output offsets) is a pending match whose output reaches into that source. A match
@@ -887,12 +805,10 @@ __device__ __forceinline__ bool exec_batch(SM &S, const OutMap &O, uint64_t cap,
   // copied by the whole wave one after another, short ones by their own lane.
   const int32_t s_rel = (int32_t)(msrc - pos);                   // source start, batch-relative
   const int32_t e_rel = s_rel + (int32_t)min(mlen, md);          // source end
-#if ZG_INFLATE_RANGE
   // The symbols whose output overlaps the source are an index range [lo, hi] (output offsets
   // are monotonic): hi = the last symbol starting before e_rel, lo = the last starting at or
   // before s_rel; both found by one interleaved binary search per batch. A round then tests
   // the pending mask against the range, with no LDS read.
-#if ZG_INFLATE_PIV
   // Two-level search without a chain of dependent LDS reads: the entries 0, 8, .., 56 (uniform,
   // by readlane) pick the 8-entry segment, one 16-B LDS read of that segment finishes it. Lanes
   // past the batch hold 0xFFFF (above any query).
@@ -922,32 +838,7 @@ __device__ __forceinline__ bool exec_batch(SM &S, const OutMap &O, uint64_t cap,
     hi = 8 * (a - 1) + ca - 1;
     lo = b > 0 ? 8 * (b - 1) + cb - 1 : 0;
   }
-#else
-  if (mine) S.rbeg[lane] = (uint16_t)(mypos - pos);
-  wsync();
-  int32_t hi = -1, lo = 0;
-  if (is_match && e_rel > 0) {
-    hi = 0;
-#pragma unroll
-    for (int32_t step = 32; step; step >>= 1) {
-      if (hi + step < (int32_t)cnt && (int32_t)S.rbeg[hi + step] < e_rel) hi += step;
-      if (lo + step < (int32_t)cnt && (int32_t)S.rbeg[lo + step] <= s_rel) lo += step;
-    }
-  }
-#endif
   const uint64_t rmask = hi < 0 ? 0ull : (hi >= 63 ? ~0ull : ((2ull << hi) - 1)) & ~((1ull << lo) - 1);
-#else
-  if (mine) S.rend[lane] = (uint16_t)(mypos - pos + (is_match ? mlen : 1u));
-  if (mine) S.rbeg[lane] = (uint16_t)(mypos - pos);
-  wsync();
-  int32_t hi = -1;  // the last symbol that starts before e_rel
-  if (is_match && e_rel > 0) {
-    hi = 0;
-#pragma unroll
-    for (int32_t step = 32; step; step >>= 1)
-      if (hi + step < (int32_t)cnt && (int32_t)S.rbeg[hi + step] < e_rel) hi += step;
-  }
-#endif
   bool pending = is_match;
   uint64_t pm;
   XPROF(6, 1);
@@ -956,14 +847,7 @@ __device__ __forceinline__ bool exec_batch(SM &S, const OutMap &O, uint64_t cap,
     XPROF(5, 1);
     bool ready = false;
     if (pending) {
-#if ZG_EXP_ONEROUND  // lab experiment only (wrong output): every match ready in the first round
-      ready = true;
-#elif ZG_INFLATE_RANGE
       ready = (pm & rmask) == 0;
-#else
-      const uint64_t m = hi < 0 ? 0ull : pm & (hi >= 63 ? ~0ull : ((2ull << hi) - 1));
-      ready = m == 0 || (int32_t)S.rend[63 - __builtin_clzll(m)] <= s_rel;
-#endif
     }
     const uint64_t lm = __ballot(ready && mlen > 32);
     if (lm) {  // the first long ready match, by the whole wave (the others wait a round)
@@ -995,7 +879,6 @@ __device__ __forceinline__ bool exec_batch(SM &S, const OutMap &O, uint64_t cap,
     if (lm && lane == __builtin_ctzll(lm)) pending = false;
     ready = ready && mlen <= 32;
     const bool in_ring = msrc + RING >= batch_end;
-#if ZG_INFLATE_XW == 8
     if (ready && in_ring && mlen <= 8) {
       // a short match whose source is in the ring (99 % of C3's): the 8 bytes from the source start
       // as two byte-aligned words of three aligned ring reads, byte k of the copy = source byte
@@ -1014,24 +897,6 @@ __device__ __forceinline__ bool exec_batch(SM &S, const OutMap &O, uint64_t cap,
       }
       pending = false;
     } else
-#elif ZG_INFLATE_XW
-    if (ready && in_ring && md >= mlen && mlen <= ZG_INFLATE_XW) {
-      // a short source wholly in the ring, not overlapping the copy: aligned ring words (all
-      // loads in flight together), byte-aligned in registers
-      const uint32_t a0 = (uint32_t)(msrc >> 2), sh = (uint32_t)(msrc & 3), nw = (sh + mlen + 3) >> 2;
-      uint32_t w[ZG_INFLATE_XW / 4 + 1];
-#pragma unroll
-      for (uint32_t j = 0; j <= ZG_INFLATE_XW / 4; j++) w[j] = j < nw ? S.ring32[(a0 + j) & (RING / 4 - 1)] : 0u;
-#pragma unroll
-      for (uint32_t j = 0; j < ZG_INFLATE_XW / 4; j++) {
-        const uint32_t v = __builtin_amdgcn_alignbyte(w[j + 1], w[j], sh);
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++)
-          if (4 * j + k < mlen) S.ring[(mypos + 4 * j + k) & RMASK] = (uint8_t)(v >> (8 * k));
-      }
-      pending = false;
-    } else
-#endif
     if (ready) {
       // byte i of the copy takes source byte i mod d: the remainder advanced per byte (no division)
       uint32_t r = 0;
@@ -1051,95 +916,6 @@ __device__ __forceinline__ bool exec_batch(SM &S, const OutMap &O, uint64_t cap,
       pending = false;
     }
   }
-#else
-  // Matches resolve in rounds: every pending match whose source lies entirely before the first
-  // pending match (or that IS the first one) copies its bytes itself; dest byte i takes source
-  // byte msrc + (i mod d), which is always final, so a lane's copy has no inner dependency.
-  bool pending = is_match;
-  uint64_t pm;
-  XPROF(6, 1);
-  XPROF(7, cnt);
-  while ((pm = __ballot(pending)) != 0) {
-    XPROF(5, 1);
-    const int first = __builtin_ctzll(pm);
-    const uint32_t F_lo = __builtin_amdgcn_readlane((uint32_t)mypos, first);
-    const uint32_t F_hi = __builtin_amdgcn_readlane((uint32_t)(mypos >> 32), first);
-    const uint64_t F = ((uint64_t)F_hi << 32) | F_lo;
-    const uint32_t flen = __builtin_amdgcn_readlane(mlen, first);
-    if (flen > 32) {  // a long match: copied by the whole wave once it is the first pending
-      const uint32_t fd = __builtin_amdgcn_readlane(md, first);
-      const float inv = 1.0f / (float)fd;
-      for (uint32_t i = lane; i < flen; i += 64) {
-        uint32_t q = (uint32_t)((float)i * inv);
-        int32_t rm = (int32_t)i - (int32_t)(q * fd);
-        if (rm < 0) rm += fd;
-        if (rm >= (int32_t)fd) rm -= fd;
-        const uint64_t src = F - fd + (uint32_t)rm;
-        const uint8_t v = (src + RING >= batch_end) ? S.ring[src & RMASK] : __builtin_nontemporal_load(O.rd(src));
-        S.ring[(F + i) & RMASK] = v;
-      }
-      if (lane == first) pending = false;
-      continue;
-    }
-    const bool ready = pending && mlen <= 32 && (lane == first || msrc + mlen <= F);
-    const bool in_ring = msrc + RING >= batch_end;
-#if ZG_INFLATE_XW == 8
-    if (ready && in_ring && mlen <= 8) {
-      // a short match whose source is in the ring (99 % of C3's): the 8 bytes from the source start
-      // as two byte-aligned words of three aligned ring reads, byte k of the copy = source byte
-      // k mod d (an overlapping copy repeats its period); 8 unconditional byte stores, the ones past
-      // the match's length into a sink byte (no exec-mask branches)
-      const uint32_t a0 = (uint32_t)(msrc >> 2), sh = (uint32_t)(msrc & 3);
-      const uint32_t w0 = S.ring32[a0 & (RING / 4 - 1)], w1 = S.ring32[(a0 + 1) & (RING / 4 - 1)],
-                     w2 = S.ring32[(a0 + 2) & (RING / 4 - 1)];
-      const uint64_t V = ((uint64_t)__builtin_amdgcn_alignbyte(w2, w1, sh) << 32) | __builtin_amdgcn_alignbyte(w1, w0, sh);
-      uint32_t r = 0;
-#pragma unroll
-      for (uint32_t k = 0; k < 8; k++) {
-        uint8_t *dst = k < mlen ? &S.ring[(mypos + k) & RMASK] : &S.sink[0];
-        *dst = (uint8_t)(V >> (8 * r));
-        r = r + 1 == md ? 0u : r + 1;
-      }
-      pending = false;
-    } else
-#elif ZG_INFLATE_XW
-    if (ready && in_ring && md >= mlen && mlen <= ZG_INFLATE_XW) {
-      // a short source wholly in the ring, not overlapping the copy: aligned ring words (all
-      // loads in flight together), byte-aligned in registers
-      const uint32_t a0 = (uint32_t)(msrc >> 2), sh = (uint32_t)(msrc & 3), nw = (sh + mlen + 3) >> 2;
-      uint32_t w[ZG_INFLATE_XW / 4 + 1];
-#pragma unroll
-      for (uint32_t j = 0; j <= ZG_INFLATE_XW / 4; j++) w[j] = j < nw ? S.ring32[(a0 + j) & (RING / 4 - 1)] : 0u;
-#pragma unroll
-      for (uint32_t j = 0; j < ZG_INFLATE_XW / 4; j++) {
-        const uint32_t v = __builtin_amdgcn_alignbyte(w[j + 1], w[j], sh);
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++)
-          if (4 * j + k < mlen) S.ring[(mypos + 4 * j + k) & RMASK] = (uint8_t)(v >> (8 * k));
-      }
-      pending = false;
-    } else
-#endif
-    if (ready) {
-      // byte i of the copy takes source byte i mod d: the remainder advanced per byte (no division)
-      uint32_t r = 0;
-      for (uint32_t i0 = 0; i0 < mlen; i0 += 4) {
-        uint8_t v[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const uint32_t i = i0 + k;
-          const uint64_t src = msrc + r;
-          v[k] = (i < mlen) ? (in_ring ? S.ring[src & RMASK] : __builtin_nontemporal_load(O.rd(src))) : 0;
-          r = r + 1 == md ? 0u : r + 1;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (i0 + k < mlen) S.ring[(mypos + i0 + k) & RMASK] = v[k];
-      }
-      pending = false;
-    }
-  }
-#endif
   pos = batch_end;
   if (pos - flushed >= FLUSH_MIN) {
     wsync();
@@ -1171,9 +947,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
   static_assert(!(ZLIB && PIPE), "the pipelined mode is for gzip streams");
   static_assert(ZLIB || !PLAN, "PLAN selects the zlib kernel's items");
   __shared__ std::conditional_t<PIPE, SmemP, Smem> S;
-#if !ZG_INFLATE_XFETCH
-  __shared__ uint16_t seg_base[65], seg_skip[64];
-#endif
   PROF_DECL;
   PROF_T(t_all);
   const uint32_t item = order ? order[blockIdx.x] : blockIdx.x;
@@ -1449,7 +1222,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
       // code lengths for literal/length + distance alphabets (ltab used as a 128-entry 7-bit table)
       uint32_t n = 0, prev = 0;
       const uint32_t total = hlit + hdist;
-#if ZG_INFLATE_PCL
       // Lane-parallel, as the lookahead symbol decode: lane l decodes the code-length symbol (code +
       // repeat bits, <= 14 bits) that would start at bit bp + l of a 63-bit window, the window's
       // symbols are chained by pointer jumping, their runs placed by a prefix sum and written at
@@ -1529,38 +1301,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
         if (!err) bits_seek_in(B, bp);
         wsync();
       }
-#else
-      while (n < total) {
-        bits_refill(B);
-        const uint32_t e = U(S.ltab[bits_peek(B, 7)]);
-        bits_drop(B, e & 15);
-        const uint32_t sym = e >> 16;
-        uint32_t rep = 0, val = 0;
-        if (sym < 16) {
-          val = sym;
-          rep = 1;
-          prev = sym;
-        } else if (sym == 16) {
-          if (n == 0) { err = ZG_CORRUPT_STREAM; break; }
-          val = prev;
-          rep = 3 + bits_get(B, 2);
-        } else if (sym == 17) {
-          rep = 3 + bits_get(B, 3);
-          val = 0;
-          prev = 0;
-        } else {
-          rep = 11 + bits_get(B, 7);
-          val = 0;
-          prev = 0;
-        }
-        if (n + rep > total) { err = ZG_CORRUPT_STREAM; break; }
-        for (uint32_t k = lane; k < rep; k += 64) {
-          const uint32_t s = n + k;
-          S.lens[s < hlit ? s : 288 + (s - hlit)] = (uint8_t)val;
-        }
-        n += rep;
-      }
-#endif
       if (err) break;
       // zero the unused tails so the table builders see exactly hlit / hdist symbols
       for (uint32_t s = lane; s < 320; s += 64) {
@@ -1582,7 +1322,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
     (void)hdist;
 
     bool eob = false;
-#if ZG_INFLATE_SEG
     // ---- segmented rounds: lane l decodes the stream region [r0 + l*SEGB, r0 + (l+1)*SEGB) serially,
     // starting OVL bits early so that its chain has met the true one by then (Huffman codes
     // self-synchronise); lane l is right once the true chain's exit from lane l-1's region is a
@@ -1650,7 +1389,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
         const uint32_t cnt_l = (lane < J) ? n - skip : 0u;
         const uint32_t incl = wave_incl_sum(cnt_l);
         const uint32_t total = U(__builtin_amdgcn_readlane((int)incl, 63));
-#if ZG_INFLATE_XFETCH
         const uint32_t rb_l = incl - cnt_l;
         const uint32_t ro_l = (uint32_t)lane * SEGCAP + skip;  // in this stream's 64 record slots
         if constexpr (PIPE) {
@@ -1694,26 +1432,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
           const uint32_t idx = g + (uint32_t)lane;
           const uint32_t rec = rec_next;
           const uint32_t ln = idx < total ? ((rec >> 31) ? (rec & 511) : 1u) : 0u;
-#else
-        seg_base[lane] = (uint16_t)(incl - cnt_l);
-        seg_skip[lane] = (uint16_t)skip;
-        if (lane == 63) seg_base[64] = (uint16_t)incl;
-        __threadfence_block();  // the records (global) and bases (LDS) before other lanes read them
-        wsync();
-        PROF_ADD(1, t_sd);
-        PROF_T(t_sx);
-        for (uint32_t g = 0; g < total && !err;) {
-          const uint32_t idx = g + (uint32_t)lane;
-          uint32_t rec = 0, ln = 0;
-          if (idx < total) {
-            int k = 0;  // the lane region holding symbol idx: the last k with seg_base[k] <= idx
-#pragma unroll
-            for (int step = 32; step; step >>= 1)
-              if (k + step < 64 && seg_base[k + step] <= idx) k += step;
-            rec = seg_scr[((uint64_t)blockIdx.x * 64 + (uint32_t)k) * SEGCAP + seg_skip[k] + (idx - seg_base[k])];
-            ln = (rec >> 31) ? (rec & 511) : 1u;
-          }
-#endif
           const uint32_t inc = wave_incl_sum(ln);
           const bool take = idx < total && inc - ln < (uint32_t)BATCH_CAP;
           const uint64_t tm = __ballot(take);
@@ -1725,13 +1443,8 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
           }
           PROF_CNT(7, bc);
           PROF_CNT(6, 1);
-#if ZG_INFLATE_XFETCH
           if (g + bc < total) rec_next = fetch(g + bc);  // in flight while this batch executes
-#endif
-#if ZG_EXP_NOEXEC  // lab experiment only (wrong output): records fetched and batched, not executed
-          pos += bytes;
-          if (__ballot(rec == 0xFFFFFFFFu)) err = ZG_CORRUPT_STREAM;
-#elif defined(ZG_PROFILE)
+#ifdef ZG_PROFILE
           if (!exec_batch(S, O, cap, pos, flushed, bc, bytes, rec, prof_acc)) err = ZG_CORRUPT_STREAM;
 #else
           if (!exec_batch(S, O, cap, pos, flushed, bc, bytes, rec, nullptr)) err = ZG_CORRUPT_STREAM;
@@ -1757,7 +1470,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
       if (err) break;
       if (!fallback) continue;  // the block is done (its end-of-block code consumed)
     }
-#endif
     // ---- symbol batches ----
     if (PIPE && !eob && !err && !held) dsync();  // wave 0 executes these batches itself
     while (!eob && !err) {
@@ -1778,7 +1490,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
         const uint32_t a2 = wi == 0 ? W2 : (wi == 1 ? W3 : W4);
         uint32_t info, rec;
         lane_symbol(S, __builtin_amdgcn_alignbit(a1, a0, bit & 31), __builtin_amdgcn_alignbit(a2, a1, bit & 31), info, rec);
-#if ZG_INFLATE_PJ
         // Chain the window's symbols by pointer jumping, with no per-symbol scalar work: J_k(x) is
         // the bit offset 2^k symbols after offset x (64: past the window, or after a stop symbol);
         // lane t composes the J_k of the bits of t into p = the offset of the window's t-th symbol,
@@ -1828,32 +1539,6 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
           }
         }
         bp += o;
-#else
-        uint64_t chain = 0;
-        uint32_t o = 0, n = 0;
-        bool slow = false;
-        while (o < 64 && cnt + n < 64 && bytes < BATCH_CAP) {
-          const uint32_t a = U(__builtin_amdgcn_readlane(info, o));
-          if (a >= F_EOB) {
-            if (a == (F_EOB | (a & 255))) {
-              o += a & 255;
-              eob = true;
-            } else if (a & F_BAD) {
-              err = ZG_CORRUPT_STREAM;
-            } else {
-              slow = true;
-            }
-            break;
-          }
-          chain |= 1ull << o;
-          n++;
-          bytes += a >> 8;
-          o += a & 255;
-        }
-        if ((chain >> lane) & 1) S.rec[cnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(chain >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)chain, 0u))] = rec;
-        cnt += n;
-        bp += o;
-#endif
         if (slow && !err && cnt < 64 && bytes < BATCH_CAP) {
           // one symbol through the canonical slow path (codes longer than the root)
           bits_seek_in(B, bp);
@@ -1955,11 +1640,7 @@ __global__ __launch_bounds__(PIPE ? 128 : 64) __attribute__((amdgpu_waves_per_eu
         wsync();
         PROF_T(t_crc);
         wave_crc_tables(S.crc, POLY_CRC32);
-#if ZG_GZ_DIRECT_READS
-        const uint32_t c = wave_crc_map(O, pos, S.crc, POLY_CRC32);
-#else
         const uint32_t c = wave_crc(out, pos, S.crc, POLY_CRC32);
-#endif
         PROF_ADD(11, t_crc);
         if (c != crc || isz != (uint32_t)pos) err = ZG_CORRUPT_STREAM;
       }
@@ -2033,7 +1714,7 @@ uint32_t gzip_pipe_max() {
 uint64_t gzip_seg_scratch_bytes(uint32_t n_items) {
   static const bool on = [] {
     const char *e = std::getenv("ZGPU_GZIP_SEG");
-    return ZG_INFLATE_SEG && (!e || std::atoi(e) != 0);
+    return !e || std::atoi(e) != 0;
   }();
   // the pipelined kernel double-buffers a stream's record slots
   const uint64_t slots = (uint64_t)n_items + std::min<uint64_t>(n_items, GZIP_PIPE_CAP);

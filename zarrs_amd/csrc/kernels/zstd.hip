@@ -43,7 +43,7 @@ __device__ unsigned long long g_zprof[13];
 #endif
 #ifdef ZG_SQ_PROFILE
 // lab-only sequence-decoder profile: [0] table-build clocks, [1] decode clocks, [2] sequences,
-// [3] blocks with sequences, [4] epochs (lane-group decoder), [5] records visited
+// [3] blocks with sequences, [4] unused (the removed lane-group decoder's epochs), [5] records visited
 __device__ unsigned long long g_sqprof[20];  // [8 + 4 t + mode]: table modes (LL, OF, ML) in the scan
 #define SQP_T(v) const uint64_t v = clock64()
 #define SQP_ADD(slot, x) do { if (__lane_id() == 0) atomicAdd(&g_sqprof[slot], (unsigned long long)(x)); } while (0)
@@ -62,9 +62,6 @@ constexpr uint32_t MAX_HUF_LOG = 12;
 // a block's Huffman decoding table in the literal scratch, right before its literals: 2^12 u16
 // entries + a 16-B header holding the table log (0: invalid description)
 constexpr uint32_t HUF_TAB = (1u << MAX_HUF_LOG) * 2 + 16;
-#ifndef ZG_HUF_SPLIT
-#define ZG_HUF_SPLIT 1  // Huffman tables built by k_zstd_huf (one wave per block) ahead of k_zstd_lits
-#endif
 // per-item decode mode chosen by k_zstd_scan
 constexpr uint32_t ZMODE_PARALLEL = 0, ZMODE_SERIAL = 1, ZMODE_SKIP = 2;
 
@@ -1205,38 +1202,16 @@ struct ZScanSmem {
   int16_t norm[64];
 };
 
-// literals (Huffman table) and sequences (FSE tables) are decoded one after the other: the two
-// table sets share LDS
-// sequence decoding table entry: the code's value base and extra-bit count with the FSE transition
-// (one 8-byte LDS read per table per sequence); nbx == 0xFF marks a code outside the format
-struct SeqX {
-  uint32_t base;
-  uint16_t next;
-  uint8_t nb, nbx;
-};
 #ifndef ZG_BLK_WPE
 #define ZG_BLK_WPE 6  // waves per SIMD k_zstd_blocks is compiled for
 #endif
-#ifndef ZG_SEQ_PACK
-#define ZG_SEQ_PACK 1  // 4-byte sequence tables (below); 0: 8-byte SeqX
-#endif
-#ifndef ZG_SEQ_REP_SEL
-#define ZG_SEQ_REP_SEL 0  // 1: repeat-offset update as selects (lab A/B r04ae: blocks 3.60 -> 3.94-4.17 ms, off)
-#endif
-#ifndef ZG_SEQ_SPLIT
-#define ZG_SEQ_SPLIT 1  // k_zstd_blocks walks only the FSE state chain; fields and reps per 64-batch by lanes
-#endif
-#ifndef ZG_SEQ_ONE_FSE
-#define ZG_SEQ_ONE_FSE 1  // one FSE scratch table, folded into its SeqX table at once (0: three tables)
-#endif
-#if ZG_SEQ_PACK
 // 4-byte sequence decoding entry: bits 0-8 next state base, 9-12 state bits, 13-17 value extra bits,
 // 18-23 code (LL/ML: index of its value base; OF: the offset code itself, value base 1 << code), bit
 // 31 a code outside the format. Everything the bit stream's order depends on (state and extra bit
 // counts) is in the entry; the LL/ML value base is a scalar constant load off that critical chain.
 // Each table is built as FSE entries in place (also 4 bytes) and repacked entry by entry, so the
-// three tables take 5 KiB of LDS (the 8-byte SeqX tables and their FSE scratch took 12 KiB): ~2x
-// the waves per CU for this latency-bound serial decoder.
+// three tables take 5 KiB of LDS (8-byte entries holding the value base, with their FSE scratch,
+// took 12 KiB): ~2x the waves per CU for this latency-bound serial decoder.
 constexpr uint32_t SQ_BAD = 0x80000000u;
 __device__ __forceinline__ uint32_t sq_pack(uint32_t next, uint32_t nb, uint32_t nbx, uint32_t code) {
   return next | (nb << 9) | (nbx << 13) | (code << 18);
@@ -1246,22 +1221,7 @@ struct ZDecSmem {
   int16_t norm[64];
   uint32_t tmp[32];
 };
-#else
-struct ZDecSmem {
-#if ZG_SEQ_ONE_FSE
-  Fse fse[512];  // one FSE table at a time: built, then folded into its SeqX table
-#else
-  Fse ll[512], ml[512], of[256];
-#endif
-  SeqX xl[512], xm[512], xo[256];
-  int16_t norm[64];
-  uint32_t tmp[32];
-};
-#endif
 
-
-
-__device__ __forceinline__ uint32_t sym_dec(uint32_t x) { return (x & ZSYM) ? x + 1 : x - 1; }
 __device__ __forceinline__ uint32_t sym_eval(uint32_t x, uint32_t r0, uint32_t r1, uint32_t r2) {
   if (!(x & ZSYM)) return x;
   const uint32_t slot = (x >> 24) & 3, minus = x & 0xFFFFFF;
@@ -1411,9 +1371,7 @@ __device__ __attribute__((noinline)) void scan_uniform(ZScanSmem &S, uint32_t it
           p += csize;
         }
         if (ltype != 0) {  // rle / huffman literals are materialised in the literal scratch
-#if ZG_HUF_SPLIT
           if (ltype >= 2) lit_used = ((lit_used + 15) & ~(uint64_t)15) + HUF_TAB;  // the block's table
-#endif
           R.lit_buf = (uint32_t)lit_used;
           lit_used += regen;
           if (lit_used > lit_stride) { serial = true; break; }
@@ -1743,9 +1701,7 @@ __global__ __launch_bounds__(64) void k_zstd_scan(const ZgItem *items, uint32_t 
       }
       uint32_t lit_buf = 0;
       if (ltype != 0) {  // rle / huffman literals are materialised in the literal scratch
-#if ZG_HUF_SPLIT
         if (ltype >= 2) lit_used = ((lit_used + 15) & ~(uint64_t)15) + HUF_TAB;  // the block's table
-#endif
         lit_buf = (uint32_t)lit_used;
         lit_used += regen;
         if (lit_used > lit_stride) { serial = true; break; }
@@ -1844,13 +1800,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ZG_BLK_WPE, 
       uint32_t lg[3] = {0, 0, 0};
       for (int t = 0; t < 3 && !bad; t++) {
         const uint32_t mode = (tm >> (2 * t)) & 3, off = U(Bp->tab_off[t]);
-#if ZG_SEQ_PACK
         Fse *T = (Fse *)(t == 0 ? S.xl : t == 1 ? S.xo : S.xm);  // built in place, repacked below
-#elif ZG_SEQ_ONE_FSE
-        Fse *T = S.fse;
-#else
-        Fse *T = t == 0 ? S.ll : t == 1 ? S.of : S.ml;
-#endif
         const uint32_t maxs = t == 0 ? 35 : t == 1 ? 31 : 52, maxl = t == 0 ? 9 : t == 1 ? 8 : 9;
         if (mode == 0) {
           if (t == 0) { build_fse_default(T, c_ll_def, 36, 6, S.norm, S.tmp); lg[t] = 6; }
@@ -1885,37 +1835,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ZG_BLK_WPE, 
         __syncthreads();
         for (uint32_t u = lane; u < (1u << lg[t]); u += 64) {
           const Fse e = T[u];
-#if ZG_SEQ_PACK
           uint32_t x;
           if (t == 0) x = e.sym <= 35 ? sq_pack(e.base, e.nb, c_ll_bits[e.sym], e.sym) : SQ_BAD;
           else if (t == 1) x = e.sym <= 31 ? sq_pack(e.base, e.nb, e.sym, e.sym) : SQ_BAD;
           else x = e.sym <= 52 ? sq_pack(e.base, e.nb, c_ml_bits[e.sym], e.sym) : SQ_BAD;
           ((uint32_t *)T)[u] = x;  // same entry, same lane: in place
-#else
-          if (t == 0) {
-            const bool ok = e.sym <= 35;
-            S.xl[u] = SeqX{ok ? c_ll_base[e.sym] : 0u, e.base, e.nb, (uint8_t)(ok ? c_ll_bits[e.sym] : 0xFF)};
-          } else if (t == 1) {
-            const bool ok = e.sym <= 31;
-            S.xo[u] = SeqX{ok ? (1u << e.sym) : 0u, e.base, e.nb, (uint8_t)(ok ? e.sym : 0xFF)};
-          } else {
-            const bool ok = e.sym <= 52;
-            S.xm[u] = SeqX{ok ? c_ml_base[e.sym] : 0u, e.base, e.nb, (uint8_t)(ok ? c_ml_bits[e.sym] : 0xFF)};
-          }
-#endif
         }
-        if (ZG_SEQ_ONE_FSE && !ZG_SEQ_PACK) __syncthreads();  // the next table reuses S.fse
       }
-      if (!ZG_SEQ_ONE_FSE || ZG_SEQ_PACK) __syncthreads();
+      __syncthreads();
       SQP_T(sq_t1);
       SQP_ADD(0, sq_t1 - sq_t0);
-      // Backward bit container in SGPRs: C holds bits [32 * lw, 32 * lw + have) of the aligned item
-      // words, the next unread bit at bit 63; refilled a word at a time from the BitsBack register
-      // window (readlane), so a field read is three scalar operations.
+      // the sequence section's bounds and aligned item words (the stream is read backwards)
       BitsBack R;
       if (!bad && !bb_init(R, in, it.len, U(Bp->seq_off), U(Bp->seq_end))) bad = true;
       if (!bad) {
-#if ZG_SEQ_SPLIT && ZG_SEQ_PACK
         // Split decoder. The serial part is only the FSE state chain: three table entries give every
         // bit count of the sequence, so the next three states are read positionally (one 64-bit
         // window read below the sequence's extra bits) while the entries and the bit position are
@@ -1923,8 +1856,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ZG_BLK_WPE, 
         // item words each), and the batch's repeat offsets are resolved by an inclusive scan of
         // rep-state transforms: a sequence maps the incoming (r0, r1, r2) to three values that are
         // literal offsets or ZSYM | slot << 24 | minus references to the incoming ones (the block's
-        // symbolic reps, above), and transforms compose slot by slot. The container decoder below
-        // (ZG_SEQ_SPLIT=0) spent ~120 scalar instructions a sequence on the one chain.
+        // symbolic reps, above), and transforms compose slot by slot. A decoder that read
+        // every field through one scalar bit container spent ~120 scalar instructions a sequence on
+        // the one chain; selects for the repeat-offset update measured slower there (3.60 ->
+        // 3.94-4.17 ms, lab r04ae).
         // Positions are 32-bit, relative to word kb0 of the item (a little below the stream start). The
         // chain reads its 64-bit windows by readlane from wcur = words [wb, wb + 64); wnext = words
         // [wb - 60, wb + 4) is loaded one slide ahead, so a slide (every 60 words) waits for nothing.
@@ -2088,157 +2023,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ZG_BLK_WPE, 
         }
         // the stream must end exactly on its first bit
         if (!bad && Pr != lo_r) bad = true;
-#else
-        auto word = [&](int32_t k) -> uint32_t {
-          if (k < R.wb - 16) {  // slide the window pair down, prefetching the next lower window
-            R.wb -= 64;
-            R.wcur = R.wprev;
-            R.wprev = ldw(R, R.wb - 64 + lane_id());
-          }
-          return wget(R, k);
-        };
-        const int64_t p0 = R.cur;
-        int32_t lw = (int32_t)((p0 - 1) >> 5) - 1;
-        int32_t have = (int32_t)(p0 - 32 * (int64_t)lw);  // (32, 64]
-        uint64_t C = (((uint64_t)word(lw + 1) << 32) | word(lw)) << (64 - have);
-        auto refill = [&]() {
-          if (have <= 32) {
-            lw--;
-            C |= (uint64_t)word(lw) << (32 - have);
-            have += 32;
-          }
-        };
-        auto rd = [&](uint32_t n) -> uint32_t {  // n <= 31 bits
-          const uint32_t v = (uint32_t)((C >> 1) >> (63 - n));
-          C <<= n;
-          have -= (int32_t)n;
-          return v;
-        };
-        uint32_t sll = rd(lg[0]), sof = rd(lg[1]);
-        refill();
-        uint32_t sml = rd(lg[2]);
-        uint32_t *out = seq_scratch + ((uint64_t)item * seq_cap + U(Bp->seq_buf)) * 3;
-        uint32_t remaining = nseq, done = 0;
-#if !ZG_SEQ_PACK
-        const uint2 *XO = (const uint2 *)S.xo, *XM = (const uint2 *)S.xm, *XL = (const uint2 *)S.xl;
-#endif
-        while (remaining && !bad) {
-          uint32_t r_ll = 0, r_ml = 0, r_of = 0, cnt = 0;
-          while (cnt < 64 && remaining) {
-#if ZG_SEQ_PACK
-            const uint32_t ow = U(S.xo[sof]), mw = U(S.xm[sml]), lwd = U(S.xl[sll]);
-            if ((ow | mw | lwd) & SQ_BAD) { bad = true; break; }
-            const uint32_t oc = (ow >> 18) & 63, mc = (mw >> 18) & 63, lc = (lwd >> 18) & 63;
-            refill();
-            const uint32_t ofv = (1u << oc) + rd(oc);
-            refill();
-            const uint32_t ml = c_ml_base[mc] + rd((mw >> 13) & 31);
-            const uint32_t ll = c_ll_base[lc] + rd((lwd >> 13) & 31);
-            remaining--;
-            if (remaining) {
-              refill();
-              sll = (lwd & 511) + rd((lwd >> 9) & 15);
-              sml = (mw & 511) + rd((mw >> 9) & 15);
-              sof = (ow & 511) + rd((ow >> 9) & 15);
-            }
-#else
-            const uint2 eo = XO[sof], em = XM[sml], el = XL[sll];
-            const uint32_t ob = U(eo.x), ow = U(eo.y), mb = U(em.x), mw = U(em.y), lb = U(el.x), lwd = U(el.y);
-            if ((ow | mw | lwd) & 0x80000000u) { bad = true; break; }
-            refill();
-            const uint32_t ofv = ob + rd(ow >> 24);
-            refill();
-            const uint32_t ml = mb + rd(mw >> 24);
-            const uint32_t ll = lb + rd(lwd >> 24);
-            remaining--;
-            if (remaining) {
-              refill();
-              sll = (lwd & 0xFFFF) + rd((lwd >> 16) & 0xFF);
-              sml = (mw & 0xFFFF) + rd((mw >> 16) & 0xFF);
-              sof = (ow & 0xFFFF) + rd((ow >> 16) & 0xFF);
-            }
-#endif
-            // repeat offsets, symbolically in the block's incoming rep state (RFC 8878 3.1.1.5)
-#if ZG_SEQ_REP_SEL
-            // as selects (the branchy form cost ~25 scalar instructions and four branches a sequence
-            // on a decoder bound by the CU's scalar unit): k = 0 new offset, else 1 + repeat index
-            const bool lit0 = ll == 0;
-            const uint32_t k = ofv > 3 ? 0u : ofv + (lit0 ? 1u : 0u);  // 1..4: repeat index 0..3
-            if (k == 0 && ((ofv - 3) & ZSYM)) { bad = true; break; }   // beyond any window we decode
-            const uint32_t off = k == 0 ? ofv - 3 : k == 1 ? r0 : k == 2 ? r1 : k == 3 ? r2 : sym_dec(r0);
-            const uint32_t n2 = (k == 0 || k >= 3) ? r1 : r2;  // rotations: every case but index 0/1 keeps r2
-            const uint32_t n1 = k == 1 ? r1 : r0;
-            r2 = n2;
-            r1 = n1;
-            r0 = off;
-#else
-            uint32_t off;
-            if (ofv > 3) {
-              off = ofv - 3;
-              if (off & ZSYM) { bad = true; break; }  // beyond any window we decode
-              r2 = r1; r1 = r0; r0 = off;
-            } else {
-              const uint32_t idx = ofv - 1 + (ll == 0 ? 1 : 0);
-              if (idx == 0) {
-                off = r0;
-              } else if (idx == 1) {
-                off = r1; r1 = r0; r0 = off;
-              } else if (idx == 2) {
-                off = r2; r2 = r1; r1 = r0; r0 = off;
-              } else {
-                off = sym_dec(r0); r2 = r1; r1 = r0; r0 = off;
-              }
-            }
-#endif
-            if (lane == (int)cnt) { r_ll = ll; r_ml = ml; r_of = off; }
-            sum_ll += ll;
-            sum_ml += ml;
-            cnt++;
-          }
-          if (bad) break;
-          {  // the batch's reach back from the block start (exact, per match)
-            const uint64_t bpos = sum_ll + sum_ml;  // block position after the batch
-            uint32_t inc = lane < (int)cnt ? r_ll + r_ml : 0u;
-            for (int o = 1; o < 64; o <<= 1) {
-              const uint32_t t = __shfl_up(inc, o, 64);
-              if (lane >= o) inc += t;
-            }
-            const uint32_t tot = __shfl(inc, 63, 64);
-            const int32_t p = (int32_t)(bpos - tot + inc - r_ml);  // this lane's match start
-            int32_t rc = INT32_MIN;
-            uint32_t m0 = ~0u, m1 = ~0u, m2 = ~0u;
-            if (lane < (int)cnt && r_ml) {
-              if (!(r_of & ZSYM)) {
-                rc = (int32_t)r_of - p;
-              } else {
-                const uint32_t slot = (r_of >> 24) & 3, mv = (r_of & 0xFFFFFF) + (uint32_t)p;
-                if (slot == 0) m0 = mv;
-                else if (slot == 1) m1 = mv;
-                else m2 = mv;
-              }
-            }
-            for (int o = 32; o; o >>= 1) {
-              rc = max(rc, __shfl_xor(rc, o, 64));
-              m0 = min(m0, __shfl_xor(m0, o, 64));
-              m1 = min(m1, __shfl_xor(m1, o, 64));
-              m2 = min(m2, __shfl_xor(m2, o, 64));
-            }
-            reach_c = max(reach_c, rc);
-            reach_m0 = min(reach_m0, m0);
-            reach_m1 = min(reach_m1, m1);
-            reach_m2 = min(reach_m2, m2);
-          }
-          if (lane < (int)cnt) {
-            uint32_t *o = out + (uint64_t)(done + lane) * 3;
-            o[0] = r_ll;
-            o[1] = r_ml;
-            o[2] = r_of;
-          }
-          done += cnt;
-        }
-        // the stream must end exactly on its first bit
-        if (!bad && (int64_t)lw * 32 + have != R.lo_bit) bad = true;
-#endif
       }
       SQP_T(sq_t2);
       SQP_ADD(1, sq_t2 - sq_t1);
@@ -2261,388 +2045,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ZG_BLK_WPE, 
         Bp->rep_out[2] = r2;
       }
     }
-  }
-}
-
-// -------------------------------------------------------------------------------------------------
-// Lane-group sequence decoder (ZGPU_ZSTD_SEQ=1, default): ZG_SEQ_G blocks per wave, one lane each.
-// k_zstd_blocks above runs one block per wave as wave-uniform scalar code (~120 scalar instructions a
-// sequence), and the CU's one scalar unit, shared by the ~20 waves resident on it, bounded the
-// whole decoder. Here the serial FSE chain of a block runs in one lane's vector registers, so one
-// vector instruction advances ZG_SEQ_G blocks and four SIMDs share the work: each lane has its own
-// backward bit container (refilled from a 4-word prefetch queue of its block's stream), its three
-// states, its repeat offsets (symbolic, as above) and its block's three tables, built into its own
-// slot of LDS by the whole wave before the decode (5 KiB per block). Output and record fields are
-// those of k_zstd_blocks.
-#ifndef ZG_SEQ_G
-#define ZG_SEQ_G 4
-#endif
-#ifndef ZG_SEQ_WN
-#define ZG_SEQ_WN 128  // staged stream words per block and epoch
-#endif
-#ifndef ZG_SEQ_POS
-#define ZG_SEQ_POS 0  // 1: positional field reader (lab r06p: blocks 5.01 -> 5.74 ms at 64 L0 chunks, off)
-#endif
-template <int G>
-struct ZDecLgSmem {
-  uint32_t xl[G][512], xm[G][512], xo[G][256];
-  uint32_t win[G][ZG_SEQ_WN];
-  uint32_t llb[36], mlb[53];
-  int16_t norm[64];
-  uint32_t tmp[32];
-};
-
-#ifndef ZG_SEQ_WPE
-#define ZG_SEQ_WPE 1  // lane-group decoder: minimum waves per SIMD the register allocation must allow
-#endif
-template <int G>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(ZG_SEQ_WPE, 8))) void k_zstd_blocks_lg(const ZgItem *items, uint32_t *status, ZBlk *blks,
-                                                       uint32_t blk_cap, const uint32_t *nblk, const uint32_t *zmode,
-                                                       uint32_t n_items, uint32_t *seq_scratch, uint64_t seq_cap,
-                                                       const unsigned long long *max_nblk) {
-  __shared__ ZDecLgSmem<G> S;
-  const int lane = lane_id();
-  for (int k = lane; k < 53; k += 64) {
-    if (k < 36) S.llb[k] = c_ll_base[k];
-    S.mlb[k] = c_ml_base[k];
-  }
-  const uint64_t total = (uint64_t)n_items * rec_blocks(blk_cap, max_nblk);
-  for (uint64_t g0 = (uint64_t)blockIdx.x * G; g0 < total; g0 += (uint64_t)gridDim.x * G) {
-    SQP_T(sq_t0);
-    SQP_ADD(5, G);
-    // ---- the wave builds the tables of its G records, one record at a time; lane k keeps record
-    // k's fields (block-major record order, as k_zstd_blocks)
-    bool mine = false, bad = false;
-    ZBlk *Bp = nullptr;
-    uint32_t item = 0, nseq = 0, regen = 0, lg0 = 0, lg1 = 0, lg2 = 0, seq_off = 0, seq_end = 0, seq_buf = 0;
-    for (int k = 0; k < G; k++) {
-      const uint64_t g = g0 + k;
-      if (g >= total) break;
-      const uint32_t it_k = (uint32_t)(g % n_items), bi = (uint32_t)(g / n_items);
-      if (bi >= nblk[it_k] || zmode[it_k] != ZMODE_PARALLEL) continue;
-      ZBlk *B = blks + (uint64_t)it_k * blk_cap + bi;
-      const uint32_t flags = U(B->flags);
-      if ((flags & 3) != ZB_CMP) continue;
-      const ZgItem it = items[it_k];
-      const In I{(const uint8_t *)it.src, it.len};
-      const uint32_t ns_k = U(B->nseq);
-      bool bad_k = false;
-      uint32_t lg[3] = {0, 0, 0};
-      if (ns_k) {
-        const uint32_t tm = U(B->tab_mode);
-        __syncthreads();  // the previous use of norm / tmp is done
-        for (int t = 0; t < 3 && !bad_k; t++) {
-          const uint32_t mode = (tm >> (2 * t)) & 3, off = U(B->tab_off[t]);
-          Fse *T = (Fse *)(t == 0 ? S.xl[k] : t == 1 ? S.xo[k] : S.xm[k]);  // built in place, repacked below
-          const uint32_t maxs = t == 0 ? 35 : t == 1 ? 31 : 52, maxl = t == 0 ? 9 : t == 1 ? 8 : 9;
-          if (mode == 0) {
-            if (t == 0) { build_fse_default(T, c_ll_def, 36, 6, S.norm, S.tmp); lg[t] = 6; }
-            else if (t == 1) { build_fse_default(T, c_of_def, 29, 5, S.norm, S.tmp); lg[t] = 5; }
-            else { build_fse_default(T, c_ml_def, 53, 6, S.norm, S.tmp); lg[t] = 6; }
-          } else if (mode == 1) {
-            build_fse_rle(T, I.b(off));
-            lg[t] = 0;
-          } else {
-            uint32_t acc, ns;
-            InW Ic((const uint8_t *)it.src, it.len);
-            if (!read_ncount(Ic, off, it.len - off, S.norm, maxs, maxl, acc, ns)) { bad_k = true; break; }
-            __syncthreads();
-            build_fse(T, S.norm, ns, acc, S.tmp);
-            lg[t] = acc;
-          }
-          __syncthreads();
-          for (uint32_t u = lane; u < (1u << lg[t]); u += 64) {
-            const Fse e = T[u];
-            uint32_t x;
-            if (t == 0) x = e.sym <= 35 ? sq_pack(e.base, e.nb, c_ll_bits[e.sym], e.sym) : SQ_BAD;
-            else if (t == 1) x = e.sym <= 31 ? sq_pack(e.base, e.nb, e.sym, e.sym) : SQ_BAD;
-            else x = e.sym <= 52 ? sq_pack(e.base, e.nb, c_ml_bits[e.sym], e.sym) : SQ_BAD;
-            ((uint32_t *)T)[u] = x;
-          }
-        }
-      }
-      if (lane == k) {
-        mine = true;
-        bad = bad_k;
-        Bp = B;
-        item = it_k;
-        nseq = ns_k;
-        regen = U(B->regen);
-        lg0 = lg[0];
-        lg1 = lg[1];
-        lg2 = lg[2];
-        seq_off = U(B->seq_off);
-        seq_end = U(B->seq_end);
-        seq_buf = U(B->seq_buf);
-      }
-    }
-    __syncthreads();
-    // ---- every lane decodes its own block's sequences, in epochs: the wave stages the next ZG_SEQ_WN
-    // words of each lane's stream into LDS (one coalesced load per lane and block, one wait), then
-    // each lane decodes until fewer than three staged words remain below its position (a sequence
-    // takes at most three refills). No global load inside the decode loop, so the sequence stores
-    // are never waited on, and a sequence's three table reads and three word reads issue together.
-    uint64_t sum_ll = 0, sum_ml = 0;
-    uint32_t r0 = ZSYM | (0u << 24), r1 = ZSYM | (1u << 24), r2 = ZSYM | (2u << 24);
-    int32_t reach_c = INT32_MIN;
-    uint32_t reach_m0 = ~0u, reach_m1 = ~0u, reach_m2 = ~0u;
-    const uint32_t *words = nullptr;
-    int32_t nwords = 0, lw = 0, have = 0, lo_w = 0;
-    int64_t lo_bit = 0, P = 0;  // P (ZG_SEQ_POS): stream bits not read yet; the next bit read is P - 1
-    uint64_t C = 0;
-    bool act = false;
-    uint32_t sll = 0, sof = 0, sml = 0, n = 0;
-    uint32_t *out = nullptr;
-    if (mine && !bad && nseq) {
-      const ZgItem it = items[item];
-      const uint8_t *in = (const uint8_t *)it.src;
-      const uintptr_t mis = (uintptr_t)in & 3;
-      words = (const uint32_t *)((uintptr_t)in - mis);
-      nwords = (int32_t)((it.len + mis + 3) / 4);
-      const uint32_t last = seq_end > seq_off ? in[seq_end - 1] : 0u;
-      if (last == 0) {
-        bad = true;
-      } else {
-        const int64_t p0 = (int64_t)(seq_end - 1 + mis) * 8 + highbit(last);
-        lo_bit = (int64_t)(seq_off + mis) * 8;
-        P = p0;
-        lw = (int32_t)((p0 - 1) >> 5) - 1;
-        have = (int32_t)(p0 - 32 * (int64_t)lw);  // (32, 64]
-        auto ld = [&](int32_t k) -> uint32_t { return (k >= 0 && k < nwords) ? words[k] : 0u; };
-        C = (((uint64_t)ld(lw + 1) << 32) | ld(lw)) << (64 - have);
-        act = true;
-        out = seq_scratch + ((uint64_t)item * seq_cap + seq_buf) * 3;
-      }
-    }
-    bool first = true;
-    SQP_T(sq_t1);
-    SQP_ADD(0, sq_t1 - sq_t0);
-#ifdef ZG_SQ_PROFILE
-    if (mine && nseq) {
-      atomicAdd(&g_sqprof[2], (unsigned long long)nseq);
-      atomicAdd(&g_sqprof[3], 1ull);
-    }
-#endif
-    while (__any(act)) {
-      SQP_ADD(4, 1);
-      // stage words [lw - WN, lw) of every active lane's stream: lane k's window is S.win[k]
-      // (positional reader: [kt + 1 - WN, kt + 1), kt the word holding bit P - 1)
-      lo_w = ZG_SEQ_POS ? (int32_t)((P - 1) >> 5) + 1 - ZG_SEQ_WN : lw - ZG_SEQ_WN;
-#pragma unroll
-      for (int k = 0; k < G; k++) {
-        const bool ak = __builtin_amdgcn_readlane((int)act, k) != 0;
-        if (!ak) continue;
-        const uint64_t wp = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uintptr_t)words, k)) |
-                            ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uintptr_t)words >> 32), k) << 32);
-        const int32_t nw = __builtin_amdgcn_readlane(nwords, k), b = __builtin_amdgcn_readlane(lo_w, k);
-        const uint32_t *W = (const uint32_t *)(uintptr_t)wp;
-        for (int i = lane; i < ZG_SEQ_WN; i += 64) {
-          const int32_t w = b + i;
-          S.win[k][i] = (w >= 0 && w < nw) ? W[w] : 0u;
-        }
-      }
-      __syncthreads();
-#if ZG_SEQ_POS
-      // Positional reader: a field of nb bits is stream bits [P - nb, P). A sequence reads at most
-      // 31 + 16 + 16 + 9 + 9 + 8 = 89 bits, i.e. words kt = (P - 1) >> 5 down to kt - 3: they are read
-      // from the staged window with the three table entries, in one LDS round; the six field
-      // positions follow from the entries' bit counts, and the fields are funnel-shifted out of those
-      // four words independently (the 64-bit container's refill / shift chain serialised them).
-      const uint32_t k = (uint32_t)lane;
-      auto win4 = [&](int32_t kt, uint32_t &q0, uint32_t &q1, uint32_t &q2, uint32_t &q3) {
-        const uint32_t *wk = &S.win[k][kt - 3 - lo_w];
-        q0 = wk[0];
-        q1 = wk[1];
-        q2 = wk[2];
-        q3 = wk[3];
-      };
-      // bits [q, q + nb) of the stream, nb <= 31, from words base/32 .. base/32 + 3
-      auto ext = [](int64_t q, uint32_t nb, int64_t base, uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3) -> uint32_t {
-        const uint32_t r = (uint32_t)(q - base), j = r >> 5, sh = r & 31;
-        const uint32_t lo = j == 0 ? q0 : j == 1 ? q1 : j == 2 ? q2 : q3;
-        const uint32_t hi = j == 0 ? q1 : j == 1 ? q2 : j == 2 ? q3 : 0u;
-        return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & ((1u << nb) - 1);
-      };
-      if (act && first) {  // the three initial states (at most 9 + 8 + 9 bits)
-        first = false;
-        const int32_t kt = (int32_t)((P - 1) >> 5);
-        uint32_t q0, q1, q2, q3;
-        win4(kt, q0, q1, q2, q3);
-        const int64_t base = (int64_t)(kt - 3) * 32;
-        sll = ext(P - lg0, lg0, base, q0, q1, q2, q3);
-        P -= lg0;
-        sof = ext(P - lg1, lg1, base, q0, q1, q2, q3);
-        P -= lg1;
-        sml = ext(P - lg2, lg2, base, q0, q1, q2, q3);
-        P -= lg2;
-      }
-      while (act) {
-        const int32_t kt = (int32_t)((P - 1) >> 5);
-        if (kt - 3 < lo_w) break;  // the next epoch stages the words below
-        const uint32_t ow = S.xo[k][sof], mw = S.xm[k][sml], lwd = S.xl[k][sll];
-        uint32_t q0, q1, q2, q3;
-        win4(kt, q0, q1, q2, q3);
-        if ((ow | mw | lwd) & SQ_BAD) { bad = true; act = false; break; }
-        const int64_t base = (int64_t)(kt - 3) * 32;
-        const uint32_t oc = (ow >> 18) & 63, mc = (mw >> 18) & 63, lc = (lwd >> 18) & 63;
-        const uint32_t mbits = (mw >> 13) & 31, lbits = (lwd >> 13) & 31;
-        const int64_t P1 = P - oc, P2 = P1 - mbits, P3 = P2 - lbits;
-        const uint32_t ofv = (1u << oc) + ext(P1, oc, base, q0, q1, q2, q3);
-        const uint32_t ml = S.mlb[mc] + ext(P2, mbits, base, q0, q1, q2, q3);
-        const uint32_t ll = S.llb[lc] + ext(P3, lbits, base, q0, q1, q2, q3);
-        n++;
-        P = P3;
-        if (n < nseq) {
-          const uint32_t nl = (lwd >> 9) & 15, nm = (mw >> 9) & 15, no = (ow >> 9) & 15;
-          const int64_t P4 = P3 - nl, P5 = P4 - nm, P6 = P5 - no;
-          sll = (lwd & 511) + ext(P4, nl, base, q0, q1, q2, q3);
-          sml = (mw & 511) + ext(P5, nm, base, q0, q1, q2, q3);
-          sof = (ow & 511) + ext(P6, no, base, q0, q1, q2, q3);
-          P = P6;
-        }
-        // repeat offsets, symbolically in the block's incoming rep state (RFC 8878 3.1.1.5), as
-        // selects: kk = 0 a new offset, else 1 + repeat index
-        const uint32_t kk = ofv > 3 ? 0u : ofv + (ll == 0 ? 1u : 0u);
-        if (kk == 0 && ((ofv - 3) & ZSYM)) { bad = true; act = false; break; }  // beyond any window we decode
-        const uint32_t s3 = (r0 & ZSYM) ? r0 + 1 : r0 - 1;
-        uint32_t off = ofv - 3;
-        off = kk == 1 ? r0 : off;
-        off = kk == 2 ? r1 : off;
-        off = kk == 3 ? r2 : off;
-        off = kk == 4 ? s3 : off;
-        const uint32_t n2 = (kk == 0 || kk >= 3) ? r1 : r2;
-        const uint32_t n1 = kk == 1 ? r1 : r0;
-        r2 = n2;
-        r1 = n1;
-        r0 = off;
-        // how far the match reaches back from the block start (exact, per match)
-        const int32_t p = (int32_t)(sum_ll + sum_ml + ll);
-        const bool isc = !(off & ZSYM);
-        const uint32_t slot = (off >> 24) & 3, mv = (off & 0xFFFFFF) + (uint32_t)p;
-        reach_c = isc ? max(reach_c, (int32_t)off - p) : reach_c;
-        reach_m0 = (!isc && slot == 0) ? min(reach_m0, mv) : reach_m0;
-        reach_m1 = (!isc && slot == 1) ? min(reach_m1, mv) : reach_m1;
-        reach_m2 = (!isc && slot >= 2) ? min(reach_m2, mv) : reach_m2;
-        sum_ll += ll;
-        sum_ml += ml;
-        uint32_t *o = out + (uint64_t)(n - 1) * 3;
-        o[0] = ll;
-        o[1] = ml;
-        o[2] = off;
-        if (n == nseq) {
-          act = false;
-          if (P != lo_bit) bad = true;  // the stream must end exactly on its first bit
-        }
-      }
-#else
-      if (act && first) {  // the three initial states
-        first = false;
-        // the container holds > 32 bits, at most 9 + 8 read before the refill
-        sll = (uint32_t)((C >> 1) >> (63 - lg0));
-        C <<= lg0;
-        have -= (int32_t)lg0;
-        sof = (uint32_t)((C >> 1) >> (63 - lg1));
-        C <<= lg1;
-        have -= (int32_t)lg1;
-        if (have <= 32) {
-          lw--;
-          C |= (uint64_t)S.win[lane][lw - lo_w] << (32 - have);
-          have += 32;
-        }
-        sml = (uint32_t)((C >> 1) >> (63 - lg2));
-        C <<= lg2;
-        have -= (int32_t)lg2;
-      }
-      const uint32_t k = (uint32_t)lane;
-      while (act && lw - 3 >= lo_w) {
-        // everything this sequence can read: its three table entries and the next three words
-        const uint32_t ow = S.xo[k][sof], mw = S.xm[k][sml], lwd = S.xl[k][sll];
-        uint32_t w1 = S.win[k][lw - 1 - lo_w], w2 = S.win[k][lw - 2 - lo_w], w3 = S.win[k][lw - 3 - lo_w];
-        if ((ow | mw | lwd) & SQ_BAD) { bad = true; act = false; break; }
-        auto refill = [&]() {
-          const bool nd = have <= 32;
-          C |= nd ? (uint64_t)w1 << (32 - have) : 0ull;
-          have += nd ? 32 : 0;
-          lw -= nd ? 1 : 0;
-          w1 = nd ? w2 : w1;
-          w2 = nd ? w3 : w2;
-        };
-        auto rd = [&](uint32_t nb) -> uint32_t {  // nb <= 31 bits
-          const uint32_t v = (uint32_t)((C >> 1) >> (63 - nb));
-          C <<= nb;
-          have -= (int32_t)nb;
-          return v;
-        };
-        const uint32_t oc = (ow >> 18) & 63, mc = (mw >> 18) & 63, lc = (lwd >> 18) & 63;
-        refill();
-        const uint32_t ofv = (1u << oc) + rd(oc);
-        refill();
-        const uint32_t ml = S.mlb[mc] + rd((mw >> 13) & 31);
-        const uint32_t ll = S.llb[lc] + rd((lwd >> 13) & 31);
-        n++;
-        if (n < nseq) {
-          refill();
-          sll = (lwd & 511) + rd((lwd >> 9) & 15);
-          sml = (mw & 511) + rd((mw >> 9) & 15);
-          sof = (ow & 511) + rd((ow >> 9) & 15);
-        }
-        // repeat offsets, symbolically in the block's incoming rep state (RFC 8878 3.1.1.5), as
-        // selects: kk = 0 a new offset, else 1 + repeat index
-        const uint32_t kk = ofv > 3 ? 0u : ofv + (ll == 0 ? 1u : 0u);
-        if (kk == 0 && ((ofv - 3) & ZSYM)) { bad = true; act = false; break; }  // beyond any window we decode
-        const uint32_t s3 = (r0 & ZSYM) ? r0 + 1 : r0 - 1;
-        uint32_t off = ofv - 3;
-        off = kk == 1 ? r0 : off;
-        off = kk == 2 ? r1 : off;
-        off = kk == 3 ? r2 : off;
-        off = kk == 4 ? s3 : off;
-        const uint32_t n2 = (kk == 0 || kk >= 3) ? r1 : r2;
-        const uint32_t n1 = kk == 1 ? r1 : r0;
-        r2 = n2;
-        r1 = n1;
-        r0 = off;
-        // how far the match reaches back from the block start (exact, per match)
-        const int32_t p = (int32_t)(sum_ll + sum_ml + ll);
-        const bool isc = !(off & ZSYM);
-        const uint32_t slot = (off >> 24) & 3, mv = (off & 0xFFFFFF) + (uint32_t)p;
-        reach_c = isc ? max(reach_c, (int32_t)off - p) : reach_c;
-        reach_m0 = (!isc && slot == 0) ? min(reach_m0, mv) : reach_m0;
-        reach_m1 = (!isc && slot == 1) ? min(reach_m1, mv) : reach_m1;
-        reach_m2 = (!isc && slot >= 2) ? min(reach_m2, mv) : reach_m2;
-        sum_ll += ll;
-        sum_ml += ml;
-        uint32_t *o = out + (uint64_t)(n - 1) * 3;
-        o[0] = ll;
-        o[1] = ml;
-        o[2] = off;
-        if (n == nseq) {
-          act = false;
-          // the stream must end exactly on its first bit
-          if ((int64_t)lw * 32 + have != lo_bit) bad = true;
-        }
-      }
-#endif
-      __syncthreads();  // this epoch's window reads are done before the next staging
-    }
-    SQP_T(sq_t2);
-    SQP_ADD(1, sq_t2 - sq_t1);
-    if (mine) {
-      if (!bad && sum_ll > regen) bad = true;
-      if (!bad && regen + sum_ml > BLOCK_MAX) bad = true;  // a block decodes to at most 128 KiB
-      if (bad) {
-        status[item] = ZG_CORRUPT_STREAM;
-      } else {
-        Bp->out_size = (uint32_t)(regen + sum_ml);
-        Bp->reach_c = reach_c;
-        Bp->reach_m[0] = reach_m0;
-        Bp->reach_m[1] = reach_m1;
-        Bp->reach_m[2] = reach_m2;
-        Bp->rep_out[0] = r0;
-        Bp->rep_out[1] = r1;
-        Bp->rep_out[2] = r2;
-      }
-    }
-    __syncthreads();  // the tables are rebuilt for the next records
   }
 }
 
@@ -2673,40 +2075,18 @@ constexpr int LIT_STAGE_R = ZG_LIT_WPE >= 4 ? 4 : 8;  // 16-B staging loads in f
 #ifndef ZG_LIT_GRID_PER_CU
 #define ZG_LIT_GRID_PER_CU 4
 #endif
-#ifndef ZG_LIT_PACK
-#define ZG_LIT_PACK 1  // decoded literals stored ZG_LIT_PACK_B at a time
-#endif
-#ifndef ZG_LIT_PACK_B
-#define ZG_LIT_PACK_B 8
-#endif
-#ifndef ZG_LIT_GWIN
-#define ZG_LIT_GWIN 4  // literal sections beyond LIT_LDS: 1 per-lane 16-B window, 2 32-B + prefetch,
-                       // 3 64-B + prefetch, 4 GBlk (32-B blocks moved in lockstep rounds)
-#endif
-#ifndef ZG_LIT_STAGE
-#define ZG_LIT_STAGE 1  // 1: a lane's decoded literals leave through an LDS window, stored as whole
-                        // aligned ZG_LIT_STAGE_W-B pieces (16-B stores) instead of 8-B stores
-#endif
 #ifndef ZG_LIT_STAGE_W
 #define ZG_LIT_STAGE_W 32  // staging window bytes per lane: one 32-B sector (lab PMC: literal writes
                            // 2,994 -> 643 MB per launch on 64 C5 chunks, 1.2x the literal bytes)
 #endif
-#ifndef ZG_LIT_STG_PITCH
-#define ZG_LIT_STG_PITCH (2 * ZG_LIT_STAGE_W)  // bytes per lane: two windows (pass 1's record stores are
-                                               // deferred a round, below; with the 8 KiB section stage
-                                               // the workgroup keeps 37 KB of LDS: 4 per CU)
-#endif
-#ifndef ZG_LIT_ILP
-#define ZG_LIT_ILP 1  // Huffman chains per lane (2: a lane decodes two segments, interleaved)
-#endif
-static_assert(ZG_LIT_ILP == 1 || (ZG_LIT_ILP == 2 && ZG_LIT_STAGE && ZG_LIT_PACK && ZG_LIT_PACK_B == 8),
-              "two chains per lane need the staged 8-B literal writer");
-constexpr uint32_t LIT_SEGS = LIT_THREADS * ZG_LIT_ILP;  // segments per block record
-#if ZG_LIT_STAGE
+// one Huffman chain per lane (two interleaved chains per lane measured slower and were removed)
+constexpr uint32_t LIT_SEGS = LIT_THREADS;  // segments per block record
+// a lane's decoded literals leave through an LDS window, stored as whole aligned LIT_STG_W-B pieces
 constexpr uint32_t LIT_STG_W = ZG_LIT_STAGE_W;
-constexpr uint32_t LIT_STG_PITCH = ZG_LIT_STG_PITCH;
+// bytes per lane: two windows (pass 1's record stores are deferred a round, below; with the 8 KiB
+// section stage the workgroup keeps 37 KB of LDS: 4 per CU)
+constexpr uint32_t LIT_STG_PITCH = 2 * LIT_STG_W;
 static_assert(LIT_STG_PITCH % 16 == 0 && LIT_STG_PITCH >= LIT_STG_W, "staging window pitch");
-#endif
 
 struct ZLitSmem {
   uint16_t huf[1 << MAX_HUF_LOG];
@@ -2716,12 +2096,10 @@ struct ZLitSmem {
   uint16_t hsorted[256];
   uint32_t tmp[32];
   int32_t entry[LIT_SEGS], exit_[LIT_SEGS];
-  uint32_t cnt[LIT_SEGS], wsum[4 * ZG_LIT_ILP];
+  uint32_t cnt[LIT_SEGS], wsum[4];
   uint32_t ctl[4];  // table log, flags
   uint32_t lin[LIT_LDS / 4 + 8];
-#if ZG_LIT_STAGE
   uint4 stg[LIT_SEGS * LIT_STG_PITCH / 16];  // per-segment output windows
-#endif
 };
 
 // backward bit container: C holds bits [lp, p) of the word array, bit p-1 at C bit 63
@@ -2737,14 +2115,14 @@ __device__ __forceinline__ void hl_init(HufLane &H, int32_t p, const Wd &word) {
   H.v = p - H.lp;  // (32, 64]
   H.C = V << (64 - H.v);
 }
-// word-reader hooks of hl_run: a plain reader always has the word; GBlk (below) has it only inside
+// word-reader hooks of the symbol loops: a plain reader always has the word; GBlk (below) has it only inside
 // its current block
 template <class Wd>
 __device__ __forceinline__ void wd_start(const Wd &, const HufLane &) {}
 
 // Literal-section words through a window of one 32-B block plus the block below it, moved in
-// lockstep (ZG_LIT_GWIN 4). The per-lane prefetching readers (GWordPF) let each lane switch blocks on
-// its own; but a wave's load counter is shared, so a lane switching blocks waited for every load the
+// lockstep. Per-lane prefetching readers (16-, 32- and 64-B windows, removed) let each lane switch
+// blocks on its own; but a wave's load counter is shared, so a lane switching blocks waited for every load the
 // other lanes had just issued (s_waitcnt vmcnt(0)), one memory round trip nearly every symbol step
 // (C5: ~2,000 cycles per step). Here a lane whose next word lies below its block stops; once every
 // lane of the wave has stopped or finished, the stopped lanes take the prefetched block (loaded one
@@ -2772,7 +2150,7 @@ struct GBlk {
     ld(cb, a0, a1);
     cur = 0;
   }
-  // A current again (hl_run's rounds alternate A and B in unrolled code, so no block is ever copied
+  // A current again (the symbol loops' rounds alternate A and B in unrolled code, so no block is ever copied
   // between registers in a round - a copy of a prefetched block is a wait for it)
   __device__ __forceinline__ void norm() const {
     if (cur) {
@@ -2825,18 +2203,7 @@ template <>
 struct WdBlocks<GBlk> {
   static constexpr bool value = true;
 };
-template <int P, class Wd>
-__device__ __forceinline__ bool wd_get_p(const Wd &w, int32_t k, uint32_t &out) {
-  if constexpr (WdBlocks<Wd>::value) return w.template get<P>(k, out);
-  else {
-    out = w(k);
-    return true;
-  }
-}
 
-#ifndef ZG_LIT_BF
-#define ZG_LIT_BF 1  // 1: both passes' symbol loops in straight-line form (hl_count_bf / hl_write_bf)
-#endif
 // Pass 1's loop without branches inside a step: the refill is computed every step and applied under a
 // mask, and the loop has one exit (done, or blocked on a GBlk window). The scalar unit is shared by
 // the CU's four SIMDs, and the branchy form spent ~50 scalar (exec-mask) instructions per step for
@@ -2897,7 +2264,6 @@ __device__ __forceinline__ uint32_t hl_count_bf(HufLane &H, int32_t &p, int32_t 
   return n;
 }
 
-#if ZG_LIT_STAGE
 // Pass 2 in the same form: the symbols of a lane go into 8-B words of the output aligned to 8 B; a
 // completed word is the one branch of a step (every 8th symbol): the partial head word byte by byte,
 // words before the first LIT_STG_W-aligned byte as 8-B stores, the rest through the lane's LDS
@@ -2928,12 +2294,10 @@ struct LitWords {
     } else {
       stg8[staged] = acc;
       if (++staged == LIT_STG_W / 8) {
-#ifndef ZG_LIT_NOSTORE  // lab only: the cost of the window stores (output wrong)
         uint4 *g = (uint4 *)(wp - (LIT_STG_W - 8));
         const uint4 *w = (const uint4 *)stg8;
 #pragma unroll
         for (uint32_t q = 0; q < LIT_STG_W / 16; q++) g[q] = w[q];
-#endif
         staged = 0;
       }
     }
@@ -3009,17 +2373,12 @@ __device__ __forceinline__ void hl_write_bf(HufLane &H, int32_t &p, int32_t stop
   }
   L.finish();
 }
-#endif
 
-#ifndef ZG_LIT_REC
-#define ZG_LIT_REC 1  // pass 1 keeps its symbols in a per-lane record slot; pass 2 only copies (below)
-#endif
 // Record slot per lane: REC_OWN bytes of the lane's own chain (from its entry), then REC_RB bytes of
 // a repair's true-chain prefix. A lane whose symbols do not fit decodes again (pass 2) instead.
 constexpr uint32_t REC_OWN = 1024, REC_RB = 64, REC_SLOT = REC_OWN + REC_RB;
 static_assert(REC_OWN % 8 == 0 && REC_RB % 8 == 0, "record slot words");
 
-#if ZG_LIT_STAGE && ZG_LIT_BF
 // Pass 1 with records: hl_count_bf's loop, each symbol also packed into 8-B words of the lane's slot
 // (symbol i at slot[i]; only the first REC_OWN are kept).
 template <class Wd>
@@ -3109,228 +2468,6 @@ __device__ __forceinline__ uint32_t hl_count_rec(HufLane &H, int32_t &p, int32_t
   }
   return n;
 }
-#endif
-
-// decode symbols while p > stop (at most maxn); WRITE: out[k] = symbol k
-template <bool WRITE, class Wd>
-__device__ __forceinline__ uint32_t hl_run(HufLane &H, int32_t &p, int32_t stop, uint32_t tl, const uint16_t *huf,
-                                           const Wd &word, uint8_t *out, uint32_t maxn, uint4 *stg = nullptr) {
-  uint32_t n = 0;
-  const uint32_t sh = 64 - tl;
-#if ZG_LIT_PACK
-  // symbols are stored ZG_LIT_PACK_B at a time (aligned 8- or 16-B stores; bytes up to the first
-  // boundary and the tail singly): 256 lanes writing their own segments byte by byte made every byte
-  // a partial-line write-back (PMC: ~17x the literal bytes written)
-  constexpr uint32_t PB = ZG_LIT_PACK_B;
-  uint64_t acc = 0, acc1 = 0;
-  uint32_t k = 0;
-  const uint32_t head = WRITE ? (uint32_t)((PB - ((uintptr_t)out & (PB - 1))) & (PB - 1)) : 0u;
-#if ZG_LIT_STAGE
-  // 8-B words from the first 64-B boundary on go to the lane's LDS window; a completed window leaves
-  // as four aligned 16-B stores (a whole half-line at once, no partial-line write-backs)
-  static_assert(!ZG_LIT_STAGE || ZG_LIT_PACK_B == 8, "literal staging packs 8-B words");
-  const uint32_t head64 = WRITE ? (uint32_t)((LIT_STG_W - ((uintptr_t)out & (LIT_STG_W - 1))) & (LIT_STG_W - 1)) : 0u;
-  uint64_t *stg8 = (uint64_t *)stg;
-#endif
-#endif
-  // Rounds: with a block-window reader (GBlk) a lane whose next word lies below its window stops
-  // until every lane of the wave has stopped or finished; the window then moves down one block.
-  // Other readers never stop: one round.
-  auto round = [&](auto par) -> bool {
-  constexpr int P = decltype(par)::value;
-  if constexpr (WdBlocks<Wd>::value) word.template pre<P>();
-  bool blk = false;
-  while (p > stop && n < maxn) {
-    if (H.v <= 32) {
-      uint32_t w;
-      if (!wd_get_p<P>(word, (H.lp >> 5) - 1, w)) {
-        blk = true;
-        break;
-      }
-      H.C |= (uint64_t)w << (32 - H.v);
-      H.v += 32;
-      H.lp -= 32;
-    }
-    const uint32_t e = huf[(uint32_t)(H.C >> sh)];
-    const uint32_t nb = e >> 8;
-    H.C <<= nb;
-    H.v -= (int32_t)nb;
-    p -= (int32_t)nb;
-#if ZG_LIT_PACK
-    if (WRITE) {
-      if (n < head) {
-        out[n] = (uint8_t)e;
-      } else {
-        if (PB == 16 && k >= 8) acc1 |= (uint64_t)(e & 255u) << (8 * (k - 8));
-        else acc |= (uint64_t)(e & 255u) << (8 * k);
-        if (++k == PB) {
-          if (PB == 16) {
-            *(uint4 *)(out + n - 15) = make_uint4((uint32_t)acc, (uint32_t)(acc >> 32), (uint32_t)acc1, (uint32_t)(acc1 >> 32));
-          } else {
-#if ZG_LIT_STAGE
-            const uint32_t pos = n - 7;
-            if (pos < head64) {
-              *(uint64_t *)(out + pos) = acc;
-            } else {
-              const uint32_t r = (pos - head64) & (LIT_STG_W - 1);
-              stg8[r >> 3] = acc;
-              if (r == LIT_STG_W - 8) {  // window complete: out + pos - r is W-aligned
-                uint4 *g = (uint4 *)(out + pos - r);
-#pragma unroll
-                for (uint32_t q = 0; q < LIT_STG_W / 16; q++) g[q] = stg[q];
-              }
-            }
-#else
-            *(uint64_t *)(out + n - 7) = acc;
-#endif
-          }
-          acc = acc1 = 0;
-          k = 0;
-        }
-      }
-    }
-#else
-    if (WRITE) out[n] = (uint8_t)e;
-#endif
-    n++;
-  }
-  return blk;
-  };
-  if constexpr (WdBlocks<Wd>::value) {
-    word.norm();
-    for (;;) {
-      if (!round(std::integral_constant<int, 0>{})) break;
-      word.adv();
-      if (!round(std::integral_constant<int, 1>{})) {
-        word.cur = 1;
-        break;
-      }
-      word.adv();
-    }
-  } else {
-    round(std::integral_constant<int, 0>{});
-  }
-#if ZG_LIT_PACK
-#if ZG_LIT_STAGE
-  if (WRITE && n - k > head64) {  // the staged words of the last, incomplete window
-    const uint32_t done = n - k;  // bytes stored or staged as whole words
-    const uint32_t w0 = done - ((done - head64) & (LIT_STG_W - 1));
-    for (uint32_t q = w0; q < done; q += 8) *(uint64_t *)(out + q) = stg8[((q - head64) & (LIT_STG_W - 1)) >> 3];
-  }
-#endif
-  if (WRITE)
-    for (uint32_t i = 0; i < k; i++) out[n - k + i] = (uint8_t)((i < 8 ? acc : acc1) >> (8 * (i & 7)));
-#endif
-  return n;
-}
-
-// Literal-section words read from global memory through a per-lane window: a lane walks its segment
-// backwards one word at a time, so one aligned 32-B load serves eight words (scattered 4-B loads of
-// 256 lanes fetched ~10x the section bytes from HBM), and the next lower 32 B are already in flight
-// while the current ones are decoded (the decode otherwise waits a full HBM round trip every
-// 128 bits).
-struct GWordPF {
-  const gu32 *Wp;
-  int64_t lim;
-  mutable uintptr_t cb;       // address of the cached 32-B block (1: none)
-  mutable zv4u c0, c1;        // its words 0-3, 4-7
-  mutable zv4u n0, n1;        // the block below it (prefetched)
-  mutable uintptr_t nb;       // address of the block in n0/n1 (1: none)
-  mutable bool pf;            // the block below cb is still to be prefetched
-  __device__ __forceinline__ static void ld(uintptr_t b, zv4u &x0, zv4u &x1) {
-    const __attribute__((address_space(1))) zv4u *q = (const __attribute__((address_space(1))) zv4u *)b;
-    x0 = q[0];
-    x1 = q[1];
-  }
-  // The prefetch is issued on the first call after a block switch, not at the switch: issued at the
-  // switch, next to the copy of the prefetched block into c0/c1, it made the compiler wait for the
-  // new loads at once (s_waitcnt vmcnt(0) before the block's first use, the prefetch's result moved
-  // between registers), so every switch paid a full memory round trip. Here the only load pending at
-  // a switch is the one issued seven words earlier.
-  // (The word is picked in each branch: picked after the merge, the compiler's wait for a switch's
-  // loads also covered the other branch's prefetch.)
-  __device__ __forceinline__ static uint32_t pick(const zv4u &x0, const zv4u &x1, uintptr_t a) {
-    const uint32_t i = (uint32_t)(a >> 2) & 7u;
-    const zv4u h = i < 4 ? x0 : x1;
-    const uint32_t j = i & 3u;
-    return j == 0 ? h.x : j == 1 ? h.y : j == 2 ? h.z : h.w;
-  }
-  __device__ __forceinline__ uint32_t operator()(int32_t k) const {
-    if (k < 0 || k >= lim) return 0u;
-    const uintptr_t a = (uintptr_t)(Wp + k), b = a & ~(uintptr_t)31;
-    if (b != cb) {
-      if (b == nb) {  // the next lower block: take the prefetched copy
-        c0 = n0;
-        c1 = n1;
-      } else {
-        ld(b, c0, c1);
-      }
-      cb = b;
-      nb = 1;
-      pf = b > ((uintptr_t)Wp & ~(uintptr_t)31);  // the block below still holds words of the section
-      return pick(c0, c1, a);
-    }
-    const uint32_t w = pick(c0, c1, a);
-    if (pf) {
-      ld(b - 32, n0, n1);
-      nb = b - 32;
-      pf = false;
-    }
-    return w;
-  }
-};
-
-// A 64-B window with the 64-B block below it prefetched (ZG_LIT_GWIN 3): a lane reads each 128-B line
-// of its segment in two pieces instead of four. 256 lanes per workgroup read 256 lines spread over a
-// section, and between a lane's pieces of one line L2 has usually evicted it, so every piece was a
-// fabric fetch of its own (C5 PMC: ~4x the compressed literal bytes fetched).
-struct GWordPF64 {
-  const gu32 *Wp;
-  int64_t lim;
-  mutable uintptr_t cb;  // address of the cached 64-B block (1: none)
-  mutable zv4u c[4];     // its words
-  mutable zv4u n[4];     // the block below it (prefetched)
-  __device__ __forceinline__ static void ld(uintptr_t b, zv4u *x) {
-    const __attribute__((address_space(1))) zv4u *q = (const __attribute__((address_space(1))) zv4u *)b;
-#pragma unroll
-    for (int i = 0; i < 4; i++) x[i] = q[i];
-  }
-  __device__ __forceinline__ uint32_t operator()(int32_t k) const {
-    if (k < 0 || k >= lim) return 0u;
-    const uintptr_t a = (uintptr_t)(Wp + k), b = a & ~(uintptr_t)63;
-    if (b != cb) {
-      if (b + 64 == cb) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) c[i] = n[i];
-      } else {
-        ld(b, c);
-      }
-      cb = b;
-      if (b > ((uintptr_t)Wp & ~(uintptr_t)63)) ld(b - 64, n);
-    }
-    const uint32_t i = (uint32_t)(a >> 2) & 15u;
-    const zv4u h = (i >> 2) == 0 ? c[0] : (i >> 2) == 1 ? c[1] : (i >> 2) == 2 ? c[2] : c[3];
-    const uint32_t j = i & 3u;
-    return j == 0 ? h.x : j == 1 ? h.y : j == 2 ? h.z : h.w;
-  }
-};
-
-struct GWord {
-  const gu32 *Wp;
-  int64_t lim;
-  mutable uintptr_t cb;  // address of the cached 16-B block (1: none)
-  mutable zv4u c;
-  __device__ __forceinline__ uint32_t operator()(int32_t k) const {
-    if (k < 0 || k >= lim) return 0u;
-    const uintptr_t a = (uintptr_t)(Wp + k), b = a & ~(uintptr_t)15;
-    if (b != cb) {
-      cb = b;
-      c = *(const __attribute__((address_space(1))) zv4u *)b;
-    }
-    const uint32_t i = (uint32_t)(a >> 2) & 3u;
-    return i == 0 ? c.x : i == 1 ? c.y : i == 2 ? c.z : c.w;
-  }
-};
 
 #ifdef ZG_LIT_STATS
 // lab counters (tools/lab/zstd_lab.cpp): blocks, blocks with repairs, repair rounds, lanes re-decoded,
@@ -3354,9 +2491,6 @@ __device__ unsigned long long g_litprof[8];
 // uncached word reads for the rare repair walks (the cached readers' state stays out of them)
 template <class Wd>
 __device__ __forceinline__ uint32_t word_raw(const Wd &w, int32_t k) { return w(k); }
-__device__ __forceinline__ uint32_t word_raw(const GWordPF &w, int32_t k) { return (k >= 0 && k < w.lim) ? w.Wp[k] : 0u; }
-__device__ __forceinline__ uint32_t word_raw(const GWordPF64 &w, int32_t k) { return (k >= 0 && k < w.lim) ? w.Wp[k] : 0u; }
-__device__ __forceinline__ uint32_t word_raw(const GWord &w, int32_t k) { return (k >= 0 && k < w.lim) ? w.Wp[k] : 0u; }
 __device__ __forceinline__ uint32_t word_raw(const GBlk &w, int32_t k) { return w(k); }
 template <class Wd>
 struct RawWord {
@@ -3380,13 +2514,10 @@ __device__ __forceinline__ uint32_t hl_step(HufLane &H, int32_t &p, uint32_t tl,
   return e & 255u;
 }
 
-#ifndef ZG_LIT_SYNC
-#define ZG_LIT_SYNC 1  // repair by sync-point search (0: re-decode the whole segment)
-#endif
 
 template <class Wd>
 __device__ bool lits_decode(ZLitSmem &S, const Wd &word, uint32_t nstreams, const int32_t *top, const int32_t *lob,
-                            const uint32_t *nsym, uint32_t tl, uint8_t *lit, uint32_t seg, uint8_t *slot = nullptr) {
+                            const uint32_t *nsym, uint32_t tl, uint8_t *lit, uint32_t seg, uint8_t *slot) {
   const uint32_t t = threadIdx.x;
   const uint32_t G = LIT_THREADS / nstreams;
   const uint32_t s = t / G, j = t % G;
@@ -3404,28 +2535,14 @@ __device__ bool lits_decode(ZLitSmem &S, const Wd &word, uint32_t nstreams, cons
     int32_t p = j == 0 ? T0 : min(T0, tj + LIT_WARM);
     hl_init(H, p, w1);
     wd_start(w1, H);
-#if ZG_LIT_BF
     if (j) {
       const uint32_t wn = hl_count_bf(H, p, tj, tl, S.huf, w1, 0xFFFFFFFFu);
       LS_ADD(5, wn);
       (void)wn;
     }
     S.entry[t] = p;
-#if ZG_LIT_REC && ZG_LIT_STAGE
     S.cnt[t] = slot ? hl_count_rec(H, p, tj1, tl, S.huf, w1, maxn, slot, (uint64_t *)&S.stg[t * (LIT_STG_PITCH / 16)])
                     : hl_count_bf(H, p, tj1, tl, S.huf, w1, maxn);
-#else
-    S.cnt[t] = hl_count_bf(H, p, tj1, tl, S.huf, w1, maxn);
-#endif
-#else
-    if (j) {
-      const uint32_t wn = hl_run<false>(H, p, tj, tl, S.huf, w1, nullptr, 0xFFFFFFFFu);
-      LS_ADD(5, wn);
-      (void)wn;
-    }
-    S.entry[t] = p;
-    S.cnt[t] = hl_run<false>(H, p, tj1, tl, S.huf, w1, nullptr, maxn);
-#endif
     S.exit_[t] = p;
   }
   __syncthreads();
@@ -3451,7 +2568,6 @@ __device__ bool lits_decode(ZLitSmem &S, const Wd &word, uint32_t nstreams, cons
     if (t == 0 && round == 0) LS_ADD(0, 1);
 #endif
     if (fix) {
-#if ZG_LIT_SYNC
       // The lane's own chain (from its warm-up entry) is wrong only until it meets the true chain
       // (from the predecessor's exit): walk both, always stepping the one further up the stream,
       // until they meet (the count differs by the symbols each took to get there; the exit is the
@@ -3491,16 +2607,6 @@ __device__ bool lits_decode(ZLitSmem &S, const Wd &word, uint32_t nstreams, cons
       rec_full = full_now;
       rec_nw = nw;
       rec_nt = nt;
-#else
-      HufLane H;
-      int32_t p = S.exit_[t - 1];
-      ne = p;
-      hl_init(H, p, word);
-      wd_start(word, H);
-      nc = hl_run<false>(H, p, tj1, tl, S.huf, word, nullptr, maxn);
-      rec_again = true;  // nothing recorded on this path: decode again
-      nx = p;
-#endif
     }
     if (__syncthreads_or(wrong) == 0) break;
 #ifdef ZG_LIT_STATS
@@ -3543,7 +2649,6 @@ __device__ bool lits_decode(ZLitSmem &S, const Wd &word, uint32_t nstreams, cons
   LP_T(tp3);
   LP_ADD(2, tp2, tp3);
   bool redo = c != 0;  // pass 2 (decode again, writing) for this lane
-#if ZG_LIT_REC && ZG_LIT_STAGE && ZG_LIT_BF
   // The lane's slot stores (pass 1, repairs) before its reads, and the CU's vector L1 invalidated:
   // stores do not update lines the L1 already holds, and the slot's lines were read (and cached) by
   // this lane's copy of the previous record - without the invalidate it read that record's bytes.
@@ -3596,26 +2701,6 @@ __device__ bool lits_decode(ZLitSmem &S, const Wd &word, uint32_t nstreams, cons
     }
   }
   LS_ADD(7, redo ? 1 : 0);
-#ifdef ZG_LIT_REC_DEBUG  // lab: decode each copied lane again and report the first differing byte
-  if (slot && c && !redo) {
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    const RawWord<Wd> rw{word};
-    HufLane Hd;
-    int32_t pd = S.entry[t];
-    hl_init(Hd, pd, rw);
-    const uint8_t *o = lit + (uint64_t)s * seg + off;
-    for (uint32_t i = 0; i < c; i++) {
-      const uint32_t e = hl_step(Hd, pd, tl, S.huf, rw);
-      if ((uint8_t)e != o[i]) {
-        printf("litrec: t %u s %u j %u c %u i %u exp %u got %u | cnt_own %u nw %u nt %u full %d entry %d exit %d tj %d tj1 %d\n",
-               t, s, j, c, i, e, (uint32_t)o[i], cnt_own, rec_nw, rec_nt, (int)rec_full, S.entry[t], S.exit_[t], tj, tj1);
-        break;
-      }
-    }
-  }
-#endif
-#endif
   // pass 2: decode again, writing
   if (redo) {
     const Wd w2 = word;
@@ -3623,13 +2708,7 @@ __device__ bool lits_decode(ZLitSmem &S, const Wd &word, uint32_t nstreams, cons
     int32_t p = S.entry[t];
     hl_init(H, p, w2);
     wd_start(w2, H);
-#if ZG_LIT_STAGE && ZG_LIT_BF
     hl_write_bf(H, p, tj1, tl, S.huf, w2, lit + (uint64_t)s * seg + off, c, &S.stg[t * (LIT_STG_PITCH / 16)]);
-#elif ZG_LIT_STAGE
-    hl_run<true>(H, p, tj1, tl, S.huf, w2, lit + (uint64_t)s * seg + off, c, &S.stg[t * (LIT_STG_PITCH / 16)]);
-#else
-    hl_run<true>(H, p, tj1, tl, S.huf, w2, lit + (uint64_t)s * seg + off, c);
-#endif
   }
 #ifdef ZG_LIT_PROF
   __syncthreads();
@@ -3640,263 +2719,7 @@ __device__ bool lits_decode(ZLitSmem &S, const Wd &word, uint32_t nstreams, cons
   return true;
 }
 
-#if ZG_LIT_ILP == 2
-// Two chains per lane. A symbol step is one dependent LDS table read plus ~15 instructions; with
-// one chain per lane the wave waits out that read every symbol and the SIMD issues a third of its
-// cycles (4 waves each). A lane here owns segments t and t + LIT_THREADS of the record's 512 and
-// advances both every step, so two table reads are in flight per wave.
 
-// Writer of one chain's decoded literals (hl_run<true>'s packing): bytes up to the first 8-B
-// boundary singly, then 8-B words, from the first LIT_STG_W-aligned byte on through the segment's
-// LDS window as whole aligned LIT_STG_W-B pieces.
-struct LitPack {
-  uint8_t *out;
-  uint64_t *stg8;
-  uint64_t acc;
-  uint32_t k, n, head, head64;
-  __device__ __forceinline__ void init(uint8_t *o, uint4 *stg) {
-    out = o;
-    stg8 = (uint64_t *)stg;
-    acc = 0;
-    k = n = 0;
-    head = (uint32_t)((8 - ((uintptr_t)o & 7)) & 7);
-    head64 = (uint32_t)((LIT_STG_W - ((uintptr_t)o & (LIT_STG_W - 1))) & (LIT_STG_W - 1));
-  }
-  __device__ __forceinline__ void push(uint32_t e) {
-    if (n < head) {
-      out[n] = (uint8_t)e;
-    } else {
-      acc |= (uint64_t)(e & 255u) << (8 * k);
-      if (++k == 8) {
-        const uint32_t pos = n - 7;
-        if (pos < head64) {
-          *(uint64_t *)(out + pos) = acc;
-        } else {
-          const uint32_t r = (pos - head64) & (LIT_STG_W - 1);
-          stg8[r >> 3] = acc;
-          if (r == LIT_STG_W - 8) {  // window complete: out + pos - r is W-aligned
-            uint4 *g = (uint4 *)(out + pos - r);
-            const uint4 *w = (const uint4 *)stg8;
-#pragma unroll
-            for (uint32_t q = 0; q < LIT_STG_W / 16; q++) g[q] = w[q];
-          }
-        }
-        acc = 0;
-        k = 0;
-      }
-    }
-    n++;
-  }
-  __device__ __forceinline__ void finish() {
-    if (n - k > head64) {  // the staged words of the last, incomplete window
-      const uint32_t done = n - k;
-      const uint32_t w0 = done - ((done - head64) & (LIT_STG_W - 1));
-      for (uint32_t q = w0; q < done; q += 8) *(uint64_t *)(out + q) = stg8[((q - head64) & (LIT_STG_W - 1)) >> 3];
-    }
-    for (uint32_t i = 0; i < k; i++) out[n - k + i] = (uint8_t)(acc >> (8 * i));
-  }
-};
-
-// Advance two chains while p > stop and n < maxn, each on its own word reader; both table reads of
-// a step are issued before either is used.
-template <bool WRITE, class Wd>
-__device__ __forceinline__ void hl_run2(HufLane &H0, int32_t &p0, int32_t stop0, uint32_t &n0, uint32_t max0,
-                                        const Wd &w0, HufLane &H1, int32_t &p1, int32_t stop1, uint32_t &n1,
-                                        uint32_t max1, const Wd &w1, uint32_t tl, const uint16_t *huf, LitPack *P0,
-                                        LitPack *P1) {
-  const uint32_t sh = 64 - tl;
-  bool a0 = p0 > stop0 && n0 < max0, a1 = p1 > stop1 && n1 < max1;
-  while (a0 || a1) {
-    if (a0 && H0.v <= 32) {
-      H0.C |= (uint64_t)w0((H0.lp >> 5) - 1) << (32 - H0.v);
-      H0.v += 32;
-      H0.lp -= 32;
-    }
-    if (a1 && H1.v <= 32) {
-      H1.C |= (uint64_t)w1((H1.lp >> 5) - 1) << (32 - H1.v);
-      H1.v += 32;
-      H1.lp -= 32;
-    }
-    const uint32_t e0 = huf[(uint32_t)(H0.C >> sh)], e1 = huf[(uint32_t)(H1.C >> sh)];
-    if (a0) {
-      const uint32_t nb = e0 >> 8;
-      H0.C <<= nb;
-      H0.v -= (int32_t)nb;
-      p0 -= (int32_t)nb;
-      if (WRITE) P0->push(e0);
-      n0++;
-      a0 = p0 > stop0 && n0 < max0;
-    }
-    if (a1) {
-      const uint32_t nb = e1 >> 8;
-      H1.C <<= nb;
-      H1.v -= (int32_t)nb;
-      p1 -= (int32_t)nb;
-      if (WRITE) P1->push(e1);
-      n1++;
-      a1 = p1 > stop1 && n1 < max1;
-    }
-  }
-}
-
-__device__ __forceinline__ int32_t pick4(const int32_t *a, uint32_t s) {
-  return s == 0 ? a[0] : s == 1 ? a[1] : s == 2 ? a[2] : a[3];
-}
-__device__ __forceinline__ uint32_t pick4(const uint32_t *a, uint32_t s) {
-  return s == 0 ? a[0] : s == 1 ? a[1] : s == 2 ? a[2] : a[3];
-}
-
-// lits_decode with LIT_SEGS = 512 segments (same passes, repair rule and output layout).
-template <class Wd>
-__device__ bool lits_decode2(ZLitSmem &S, const Wd &word, uint32_t nstreams, const int32_t *top, const int32_t *lob,
-                             const uint32_t *nsym, uint32_t tl, uint8_t *lit, uint32_t seg) {
-  const uint32_t t = threadIdx.x;
-  const uint32_t G = LIT_SEGS / nstreams;  // segments per stream (a multiple of 64)
-  uint32_t gi[2], si[2], ji[2], NS[2];
-  int32_t T0[2], L0[2], tj[2], tj1[2];
-#pragma unroll
-  for (int c = 0; c < 2; c++) {
-    gi[c] = t + c * LIT_THREADS;
-    si[c] = gi[c] / G;
-    ji[c] = gi[c] % G;
-    T0[c] = pick4(top, si[c]);
-    L0[c] = pick4(lob, si[c]);
-    NS[c] = pick4(nsym, si[c]);
-    const int64_t len = (int64_t)T0[c] - L0[c];
-    tj[c] = T0[c] - (int32_t)(len * ji[c] / G);
-    tj1[c] = T0[c] - (int32_t)(len * (ji[c] + 1) / G);
-  }
-  // pass 1: entry / exit / count of both segments
-  {
-    const Wd wa = word, wb = word;
-    HufLane H0, H1;
-    int32_t p0 = ji[0] == 0 ? T0[0] : min(T0[0], tj[0] + LIT_WARM);
-    int32_t p1 = ji[1] == 0 ? T0[1] : min(T0[1], tj[1] + LIT_WARM);
-    hl_init(H0, p0, wa);
-    hl_init(H1, p1, wb);
-    uint32_t n0 = 0, n1 = 0;
-    hl_run2<false>(H0, p0, ji[0] ? tj[0] : p0, n0, 0xFFFFFFFFu, wa, H1, p1, ji[1] ? tj[1] : p1, n1, 0xFFFFFFFFu, wb,
-                   tl, S.huf, nullptr, nullptr);
-    LS_ADD(5, n0 + n1);
-    S.entry[gi[0]] = p0;
-    S.entry[gi[1]] = p1;
-    n0 = n1 = 0;
-    hl_run2<false>(H0, p0, tj1[0], n0, NS[0] + 1, wa, H1, p1, tj1[1], n1, NS[1] + 1, wb, tl, S.huf, nullptr, nullptr);
-    S.cnt[gi[0]] = n0;
-    S.cnt[gi[1]] = n1;
-    S.exit_[gi[0]] = p0;
-    S.exit_[gi[1]] = p1;
-  }
-  __syncthreads();
-  // repair rounds (lits_decode's rule, per segment)
-  for (uint32_t round = 0; round < G; round++) {
-    bool wrong[2], fix[2];
-    int32_t ne[2] = {0, 0}, nx[2] = {0, 0};
-    uint32_t nc[2] = {0, 0};
-#pragma unroll
-    for (int c = 0; c < 2; c++) {
-      const uint32_t g = gi[c], j = ji[c];
-      wrong[c] = j != 0 && S.entry[g] != S.exit_[g - 1];
-      fix[c] = wrong[c] && (j <= 1 || S.entry[g - 1] == S.exit_[g - 2]);
-    }
-    __syncthreads();
-    for (int c = 0; c < 2; c++) {
-      if (!fix[c]) continue;
-      const uint32_t g = gi[c];
-      const uint32_t maxn = NS[c] + 1;
-      const RawWord<Wd> rw{word};
-      HufLane Ht, Hw;
-      int32_t pt = S.exit_[g - 1], pw = S.entry[g];
-      ne[c] = pt;
-      hl_init(Ht, pt, rw);
-      hl_init(Hw, pw, rw);
-      uint32_t nt = 0, nw = 0;
-      for (;;) {
-        if (pt == pw) {
-          nc[c] = S.cnt[g] - nw + nt;
-          nx[c] = S.exit_[g];
-          break;
-        }
-        if (pt <= tj1[c] || nt > maxn || nw > maxn) {
-          nc[c] = nt;
-          nx[c] = pt;
-          break;
-        }
-        if (pt > pw) {
-          hl_step(Ht, pt, tl, S.huf, rw);
-          nt++;
-        } else {
-          hl_step(Hw, pw, tl, S.huf, rw);
-          nw++;
-        }
-      }
-    }
-    if (__syncthreads_or(wrong[0] || wrong[1]) == 0) break;
-#pragma unroll
-    for (int c = 0; c < 2; c++)
-      if (fix[c]) {
-        S.entry[gi[c]] = ne[c];
-        S.exit_[gi[c]] = nx[c];
-        S.cnt[gi[c]] = nc[c];
-      }
-    __syncthreads();
-  }
-  // prefix sums in segment order: wave-chain k = c * 4 + wave holds segments [64k, 64k + 64)
-  const uint32_t c0 = S.cnt[gi[0]], c1 = S.cnt[gi[1]];
-  LS_ADD(4, c0 + c1);
-  LS_ADD(6, 2);
-  const uint32_t lane = lane_id(), wave = t >> 6;
-  uint32_t i0 = c0, i1 = c1;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u0 = __shfl_up(i0, o, 64), u1 = __shfl_up(i1, o, 64);
-    if ((int)lane >= o) {
-      i0 += u0;
-      i1 += u1;
-    }
-  }
-  if (lane == 63) {
-    S.wsum[wave] = i0;
-    S.wsum[4 + wave] = i1;
-  }
-  __syncthreads();
-  auto pre = [&S](uint32_t k) {  // symbols in wave-chains before k
-    uint32_t b = 0;
-    for (uint32_t q = 0; q < k; q++) b += S.wsum[q];
-    return b;
-  };
-  uint32_t off[2];
-  bool bad = false;
-#pragma unroll
-  for (int c = 0; c < 2; c++) {
-    const uint32_t g = gi[c], j = ji[c], k = c * 4 + wave;
-    const uint32_t k0 = si[c] * G / 64, k1 = (si[c] + 1) * G / 64;  // the stream's wave-chains
-    const uint32_t sb = pre(k0);
-    off[c] = pre(k) + (c ? i1 - c1 : i0 - c0) - sb;
-    if (pre(k1) - sb != NS[c]) bad = true;
-    if (S.entry[g] != (j == 0 ? T0[c] : S.exit_[g - 1])) bad = true;
-    if (j == G - 1 && S.exit_[g] != L0[c]) bad = true;
-  }
-  if (__syncthreads_or(bad)) return false;
-  // pass 2: decode again, writing
-  if (c0 || c1) {
-    const Wd wa = word, wb = word;
-    HufLane H0, H1;
-    int32_t p0 = S.entry[gi[0]], p1 = S.entry[gi[1]];
-    hl_init(H0, p0, wa);
-    hl_init(H1, p1, wb);
-    LitPack P0, P1;
-    P0.init(lit + (uint64_t)si[0] * seg + off[0], &S.stg[gi[0] * (LIT_STG_PITCH / 16)]);
-    P1.init(lit + (uint64_t)si[1] * seg + off[1], &S.stg[gi[1] * (LIT_STG_PITCH / 16)]);
-    uint32_t n0 = 0, n1 = 0;
-    hl_run2<true>(H0, p0, tj1[0], n0, c0, wa, H1, p1, tj1[1], n1, c1, wb, tl, S.huf, &P0, &P1);
-    P0.finish();
-    P1.finish();
-  }
-  return true;
-}
-#endif
-
-#if ZG_HUF_SPLIT
 struct ZHufSmem {
   uint16_t huf[1 << MAX_HUF_LOG];
   Fse wt[64];
@@ -3939,7 +2762,6 @@ __global__ __launch_bounds__(64) void k_zstd_huf(const ZgItem *items, const uint
     if (lane == 0) *(uint32_t *)(tab + (HUF_TAB - 16)) = ok ? tl : 0u;
   }
 }
-#endif
 // Blocks whose output is their literals alone (raw, rle, or compressed without sequences) depend on
 // nothing before them: k_zstd_direct writes them into the slot with the whole GPU ahead of the
 // per-item execution, which only flushes up to them and steps over (at least XDIRECT bytes: a
@@ -3961,12 +2783,6 @@ __device__ __forceinline__ bool lits_in_slot(uint32_t flags, uint32_t nseq, uint
          (uint64_t)out_off + out_size <= slot_bytes;
 }
 
-
-#if ZG_LIT_ILP == 2
-#define ZG_LITS_DECODE(...) lits_decode2(__VA_ARGS__)
-#else
-#define ZG_LITS_DECODE(...) lits_decode(__VA_ARGS__, slot)
-#endif
 __global__ __launch_bounds__(LIT_THREADS) __attribute__((amdgpu_waves_per_eu(ZG_LIT_WPE, 8))) void k_zstd_lits(const ZgItem *items, uint32_t *status, const ZBlk *blks,
                                                            uint32_t blk_cap, const uint32_t *nblk,
                                                            const uint32_t *zmode, uint32_t n_items,
@@ -3975,9 +2791,8 @@ __global__ __launch_bounds__(LIT_THREADS) __attribute__((amdgpu_waves_per_eu(ZG_
                                                            uint8_t *dst = nullptr, uint64_t slot_bytes = 0) {
   __shared__ ZLitSmem S;
   const uint32_t t = threadIdx.x;
-  // this lane's record slot (ZG_LIT_REC; nullptr: every lane decodes twice)
+  // this lane's record slot (nullptr: every lane decodes twice)
   uint8_t *const slot = lit_rec ? lit_rec + ((uint64_t)blockIdx.x * LIT_THREADS + t) * REC_SLOT : nullptr;
-  (void)slot;
   const uint64_t total = (uint64_t)n_items * rec_blocks(blk_cap, max_nblk);
   for (uint64_t g = blockIdx.x; g < total; g += gridDim.x) {
     const uint32_t item = (uint32_t)(g % n_items), bi = (uint32_t)(g / n_items);  // block-major order
@@ -4000,7 +2815,6 @@ __global__ __launch_bounds__(LIT_THREADS) __attribute__((amdgpu_waves_per_eu(ZG_
       continue;
     }
     const uint32_t lo0 = Bp->lit_off, lend = Bp->lit_end;
-#if ZG_HUF_SPLIT
     // the table k_zstd_huf built: 16-B loads, one per thread
     const uint8_t *tab = lit_s - HUF_TAB;
     const uint32_t tl = *(const uint32_t *)(tab + (HUF_TAB - 16));
@@ -4009,19 +2823,6 @@ __global__ __launch_bounds__(LIT_THREADS) __attribute__((amdgpu_waves_per_eu(ZG_
       for (uint32_t v = t; v < n16; v += LIT_THREADS) ((uint4 *)S.huf)[v] = ((const uint4 *)tab)[v];
     }
     __syncthreads();
-#else
-    const uint32_t huf_off = Bp->huf_off;
-    if (t < 64) {  // wave 0 builds the table
-      const In I{in, it.len};
-      uint32_t tl = 0;
-      const uint32_t ok = read_huffman<ZLitSmem, true>(I, huf_off, it.len - huf_off, S, tl, in, it.len);
-      if (t == 0) {
-        S.ctl[0] = ok ? tl : 0u;
-      }
-    }
-    __syncthreads();
-    const uint32_t tl = S.ctl[0];
-#endif
     bool bad = tl == 0;
     const uint32_t nstreams = (flags >> 4) & 1 ? 4 : 1;
     uint64_t s_lo[4] = {lo0, 0, 0, 0}, s_hi[4] = {lend, 0, 0, 0};
@@ -4099,22 +2900,12 @@ __global__ __launch_bounds__(LIT_THREADS) __attribute__((amdgpu_waves_per_eu(ZG_
           const uint32_t v = S.lin[in ? k : 0];
           return in ? v : 0u;
         };
-        ok = ZG_LITS_DECODE(S, word, nstreams, top, lob, s_n, tl, lit, seg);
+        ok = lits_decode(S, word, nstreams, top, lob, s_n, tl, lit, seg, slot);
       } else {
         const gu32 *Wp = (const gu32 *)(words + wbase);
         const int64_t lim = nwords_item - wbase;
-#if ZG_LIT_GWIN == 4
         const GBlk word{Wp, lim, 1, {}, {}, {}, {}, 0};
-#elif ZG_LIT_GWIN == 3
-        GWordPF64 word{Wp, lim, 1, {}, {}};
-#elif ZG_LIT_GWIN == 2
-        const GWordPF word{Wp, lim, 1, zv4u{0, 0, 0, 0}, zv4u{0, 0, 0, 0}, zv4u{0, 0, 0, 0}, zv4u{0, 0, 0, 0}, 1, false};
-#elif ZG_LIT_GWIN
-        const GWord word{Wp, lim, 1, zv4u{0, 0, 0, 0}};
-#else
-        auto word = [Wp, lim](int32_t k) -> uint32_t { return (k >= 0 && k < lim) ? Wp[k] : 0u; };
-#endif
-        ok = ZG_LITS_DECODE(S, word, nstreams, top, lob, s_n, tl, lit, seg);
+        ok = lits_decode(S, word, nstreams, top, lob, s_n, tl, lit, seg, slot);
       }
     }
     if (!ok && t == 0) status[item] = ZG_CORRUPT_STREAM;
@@ -4412,7 +3203,7 @@ uint64_t zstd_lit_rec_bytes(uint32_t &wgs) {
   }();
   static const bool on = [] {
     const char *e = std::getenv("ZGPU_ZSTD_LIT_REC");
-    return ZG_LIT_REC && (!e || std::atoi(e) != 0);
+    return !e || std::atoi(e) != 0;
   }();
   wgs = on ? (uint32_t)cap : 0u;
   return on ? cap * LIT_THREADS * REC_SLOT : 0ull;
@@ -4529,28 +3320,13 @@ static hipError_t launch_zstd_pass(ZgItem *items, uint32_t *status, uint32_t n_i
   const uint32_t bgrid = (uint32_t)std::min<uint64_t>(
       recs, blk_wpe ? (uint64_t)device_cu_count() * 4 * blk_wpe
                     : std::max<uint64_t>(g_cap, (uint64_t)device_cu_count() * 4 * ZG_BLK_WPE));
-  // sequence decoder: 0 one wave per block (k_zstd_blocks, the split chain decoder: lab 64 L0 chunks
-  // 1.63 ms against the lane groups' 5.0, C5 82.0 -> 74.7 ms, profiles/r06/r06pqr_*), 1 lane groups
-  // (k_zstd_blocks_lg, the round-5 default); ZGPU_ZSTD_SEQ forces one
   const char *xp_s = std::getenv("ZGPU_ZSTD_XPAR");
   const bool par = xwin_on && Z.ext && Z.ext_cnt && n_items <= Z.ext_items && (!xp_s || std::atoi(xp_s) != 0);
-  static const int seq_env = [] {
-    const char *e = std::getenv("ZGPU_ZSTD_SEQ");
-    return e ? std::atoi(e) : -1;
-  }();
-  const int seq_mode = seq_env >= 0 ? seq_env : 0;
+  // sequence decoder: one wave per block (the split chain decoder: lab 64 L0 chunks 1.63 ms against 5.0
+  // with four blocks per wave, one per lane; C5 82.0 -> 74.7 ms, profiles/r06/r06pqr_*)
   auto launch_seq = [&] {
-    if (seq_mode == 1) {
-      // one resident wave of the lane-group decoder: its LDS (5 KiB per block) sets the waves per CU
-      const uint64_t per_cu = std::max<uint64_t>(1, (160u << 10) / ((sizeof(ZDecLgSmem<ZG_SEQ_G>) + 1023) & ~size_t(1023)));
-      const uint64_t lrecs = (recs + ZG_SEQ_G - 1) / ZG_SEQ_G;
-      const uint32_t lg_grid = (uint32_t)std::min<uint64_t>(lrecs, (uint64_t)device_cu_count() * per_cu);
-      hipLaunchKernelGGL(k_zstd_blocks_lg<ZG_SEQ_G>, dim3(lg_grid), dim3(64), 0, sq, items, status, blks, Z.blk_cap,
-                         Z.nblk, Z.mode, n_items, Z.seq, Z.seq_cap, Z.max_nblk);
-    } else {
-      hipLaunchKernelGGL(k_zstd_blocks, dim3(bgrid), dim3(64), 0, sq, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
-                         n_items, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, Z.max_nblk, Z.norm);
-    }
+    hipLaunchKernelGGL(k_zstd_blocks, dim3(bgrid), dim3(64), 0, sq, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
+                       n_items, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, Z.max_nblk, Z.norm);
   };
   if (!lits_first) launch_seq();
   if (fork) {
@@ -4560,12 +3336,10 @@ static hipError_t launch_zstd_pass(ZgItem *items, uint32_t *status, uint32_t n_i
   if (lit_direct)  // output offsets first: the literal decoder writes literal-only blocks into the slot
     hipLaunchKernelGGL(k_zstd_plan, dim3(n_items), dim3(64), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
                        slot_bytes, xseg, Z.alias, Z.lit, Z.lit_stride);
-#if ZG_HUF_SPLIT
   hipLaunchKernelGGL(k_zstd_huf, dim3(grid), dim3(64), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode, n_items,
                      Z.lit, Z.lit_stride, Z.max_nblk);
-#endif
   // record slots: one per lane of the persistent grid (allocated for l_cap workgroups)
-  uint8_t *lit_rec = (ZG_LIT_REC && Z.lit_rec && lgrid <= Z.lit_rec_wgs) ? Z.lit_rec : nullptr;
+  uint8_t *lit_rec = (Z.lit_rec && lgrid <= Z.lit_rec_wgs) ? Z.lit_rec : nullptr;
   hipLaunchKernelGGL(k_zstd_lits, dim3(lgrid), dim3(LIT_THREADS), 0, s, items, status, blks, Z.blk_cap, Z.nblk,
                      Z.mode, n_items, Z.lit, Z.lit_stride, lit_rec, Z.max_nblk, lit_direct ? dst : nullptr, slot_bytes);
   if (lits_first) launch_seq();  // same stream: after the literal decoder
