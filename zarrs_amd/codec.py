@@ -24,6 +24,7 @@ DTYPES = {
     "bool": "|b1", "int8": "<i1", "uint8": "<u1", "int16": "<i2", "uint16": "<u2", "float16": "<f2",
     "int32": "<i4", "uint32": "<u4", "float32": "<f4", "int64": "<i8", "uint64": "<u8",
     "float64": "<f8", "complex64": "<c8", "complex128": "<c16",
+    "bfloat16": "|V2",  # numpy has no bfloat16: two opaque bytes (fill value as bytes or "0x...")
 }
 
 
@@ -40,6 +41,10 @@ def fill_value_bytes(data_type: str, fill) -> bytes:
             return int(fill, 16).to_bytes(dt.itemsize, "little")
     if isinstance(fill, (list, tuple)):
         return np.array(complex(fill[0], fill[1]), dtype=dt).tobytes()
+    if dt.kind == "V":  # opaque bytes: only zero has an obvious encoding
+        if isinstance(fill, (int, float)) and fill == 0:
+            return bytes(dt.itemsize)
+        raise ValueError(f"{data_type}: give the fill value as bytes or \"0x...\"")
     return np.array(fill, dtype=dt).tobytes()
 
 
