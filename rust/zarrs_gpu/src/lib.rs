@@ -20,7 +20,8 @@
 //! * [`ArrayGpuExt`] adds a batched `retrieve_array_subset` for arrays of any supported chain
 //!   (unsharded C2/C5-style arrays): all intersecting chunks go to the GPU in one
 //!   `zgpu_retrieve_array_subset` call (Array::retrieve_array_subset_into,
-//!   array_read_ops_common.rs:20-179).
+//!   array_read_ops_common.rs:20-179). Chains with `numcodecs.fixedscaleoffset`, `bitround` or
+//!   (unsharded) `packbits` are accepted there and by the sharding plugin's inner chains.
 //!
 //! Status codes map onto `CodecError` variants as include/zgpu.h documents.
 //!

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "../../include/zgpu.h"
+#include "kernels/value.hpp"
 
 namespace zgpu {
 
@@ -32,14 +33,115 @@ static std::shared_ptr<Chain> parse(const Json &codecs, const std::string &dt, u
 
 enum class Role { A2A, A2B, B2B };
 
+// The data type and fill value a codec is bound with (with_context): a value codec replaces them
+// with its encoded data type and fill value for every codec after it.
+struct TypeCtx {
+  std::string dt;
+  uint32_t es, comp;
+  uint8_t fill[16];
+};
+
+ZgValueType value_type_of(const std::string &n) {
+  static const char *names[] = {"int8",   "int16",  "int32",   "int64",   "uint8",   "uint16",
+                                "uint32", "uint64", "float32", "float64", "float16", "bfloat16"};
+  for (uint32_t i = 0; i < 12; i++)
+    if (n == names[i]) return (ZgValueType)i;
+  return VT_NONE;
+}
+
+uint32_t value_type_size(uint32_t vt) {
+  static const uint32_t sz[] = {1, 2, 4, 8, 1, 2, 4, 8, 4, 8, 2, 2};
+  return vt < 12 ? sz[vt] : 0;
+}
+
+// A numpy type string, with or without a byte-order character (fixedscaleoffset_codec.rs:46-54 and
+// data_type_metadata_v2_to_v3), as a Zarr V3 data type name; empty if it names none.
+static std::string numpy_to_v3(std::string s) {
+  if (!s.empty() && (s[0] == '<' || s[0] == '>' || s[0] == '|' || s[0] == '=')) s = s.substr(1);
+  static const char *tab[][2] = {{"b1", "bool"},     {"i1", "int8"},      {"i2", "int16"},      {"i4", "int32"},
+                                 {"i8", "int64"},    {"u1", "uint8"},     {"u2", "uint16"},     {"u4", "uint32"},
+                                 {"u8", "uint64"},   {"f2", "float16"},   {"f4", "float32"},    {"f8", "float64"},
+                                 {"c8", "complex64"}, {"c16", "complex128"}};
+  for (const auto &e : tab)
+    if (s == e[0]) return e[1];
+  return "";
+}
+
+template <class F>
+static void with_value_type(uint32_t vt, F &&f) {
+  switch (vt) {
+    case VT_I8: f(int8_t{}); break;
+    case VT_I16: f(int16_t{}); break;
+    case VT_I32: f(int32_t{}); break;
+    case VT_I64: f(int64_t{}); break;
+    case VT_U8: f(uint8_t{}); break;
+    case VT_U16: f(uint16_t{}); break;
+    case VT_U32: f(uint32_t{}); break;
+    case VT_U64: f(uint64_t{}); break;
+    case VT_F32: f(float{}); break;
+    default: f(double{}); break;
+  }
+}
+
+void fso_encode_element(const Codec &k, const uint8_t *in, uint8_t *out) {
+  with_value_type(k.vt_dec, [&](auto t) {
+    using T = decltype(t);
+    T x;
+    std::memcpy(&x, in, sizeof(T));
+    with_value_type(k.vt_enc, [&](auto e) {
+      using E = decltype(e);
+      const E y = fso_encode_one<T, E>(x, k.fso_offset, k.fso_scale, k.fso_astype);
+      std::memcpy(out, &y, sizeof(E));
+    });
+  });
+}
+
+static uint32_t mantissa_bits(uint32_t vt) {
+  return vt == VT_F16 ? 10 : vt == VT_BF16 ? 7 : vt == VT_F32 ? 23 : vt == VT_F64 ? 52 : 0;
+}
+
+void bitround_element(uint32_t vt, uint32_t keepbits, uint8_t *elem) {
+  const uint32_t mant = mantissa_bits(vt);
+  auto go = [&](auto u) {
+    using U = decltype(u);
+    U x;
+    std::memcpy(&x, elem, sizeof(U));
+    x = bitround_one<U>(x, keepbits, mant);
+    std::memcpy(elem, &x, sizeof(U));
+  };
+  switch (value_type_size(vt)) {
+    case 1: go(uint8_t{}); break;
+    case 2: go(uint16_t{}); break;
+    case 4: go(uint32_t{}); break;
+    default: go(uint64_t{}); break;
+  }
+}
+
+bool chain_has_value_codec(const Chain &c) {
+  for (const Codec &k : c.a2a)
+    if (is_value_codec(k.kind)) return true;
+  return c.a2b.kind == CodecKind::Sharding && c.a2b.inner && chain_has_value_codec(*c.a2b.inner);
+}
+
+uint64_t packbits_size(const Codec &k, uint64_t nelem) {
+  const uint64_t bits = nelem * (uint64_t)(k.pb_last - k.pb_first + 1) * k.pb_ncomp;
+  return (bits + 7) / 8 + (k.pb_padding ? 1 : 0);
+}
+
+// The array->array codec names (CodecChain::from_metadata sorts the entries by kind, so these are
+// bound before the array->bytes codec wherever they stand in the list).
+static bool a2a_name(const std::string &n) {
+  return n == "transpose" || n == "numcodecs.fixedscaleoffset" || n == "bitround" || n == "numcodecs.bitround" ||
+         n == "https://codec.zarrs.dev/array_to_bytes/bitround";
+}
+
 // Codec names zarrs itself creates (zarrs/src/array/codec/**: impl_extension_aliases! v3 names and
 // aliases) that this pipeline does not implement. zarrs would create and use such a codec even with
 // "must_understand": false, so it is an error here rather than a skip (skipping would decode wrongly).
 static bool zarrs_knows(const std::string &n) {
   static const char *names[] = {
-      "bitround", "numcodecs.bitround", "cast_value", "numcodecs.fixedscaleoffset", "reshape", "zarrs.squeeze",
-      "packbits", "numcodecs.pcodec", "zfp", "zarrs.zfp", "numcodecs.zfpy", "zarrs.vlen", "zarrs.vlen_v2",
-      "vlen-bytes", "vlen-utf8", "vlen-array", "zarrs.optional", "zarrs.gdeflate"};
+      "cast_value", "reshape",    "zarrs.squeeze", "numcodecs.pcodec", "zfp",       "zarrs.zfp",      "numcodecs.zfpy",
+      "zarrs.vlen", "zarrs.vlen_v2", "vlen-bytes", "vlen-utf8",        "vlen-array", "zarrs.optional", "zarrs.gdeflate"};
   for (const char *k : names)
     if (n == k) return true;
   return n.rfind("https://codec.zarrs.dev/", 0) == 0;
@@ -48,8 +150,10 @@ static bool zarrs_knows(const std::string &n) {
 // Codec::from_metadata for one entry (zarrs_codec/src/lib.rs:372-449 with the per-codec
 // configurations of zarrs_metadata_ext/src/codec/registered/*.rs). Throws ChainError when the codec
 // cannot be created (unknown name or invalid configuration).
-static Role create_codec(Codec &k, const Json *cfg, const std::string &dt, uint32_t es, uint32_t comp,
-                         const uint8_t *fill) {
+static Role create_codec(Codec &k, const Json *cfg, TypeCtx &T) {
+  const std::string &dt = T.dt;
+  const uint32_t es = T.es, comp = T.comp;
+  const uint8_t *fill = T.fill;
   auto cfg_get = [&](const char *key) -> const Json * { return cfg ? cfg->get(key) : nullptr; };
   if (k.name == "transpose") {
     k.kind = CodecKind::Transpose;
@@ -64,6 +168,97 @@ static Role create_codec(Codec &k, const Json *cfg, const std::string &dt, uint3
       k.order.push_back((uint32_t)a);
     }
     return Role::A2A;
+  }
+  if (k.name == "numcodecs.fixedscaleoffset") {
+    // FixedScaleOffsetCodecConfigurationNumcodecs (numcodecs/fixedscaleoffset.rs:17-33): offset, scale
+    // (f32), dtype, astype?; deny_unknown_fields. with_context (fixedscaleoffset_codec.rs:436-471)
+    k.kind = CodecKind::FixedScaleOffset;
+    if (!cfg || cfg->kind != Json::Obj)
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.fixedscaleoffset: missing configuration"};
+    for (const auto &kv : cfg->obj)
+      if (kv.first != "offset" && kv.first != "scale" && kv.first != "dtype" && kv.first != "astype")
+        throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.fixedscaleoffset: unknown field '" + kv.first + "'"};
+    const Json *o = cfg_get("offset"), *sc = cfg_get("scale"), *d = cfg_get("dtype"), *as = cfg_get("astype");
+    if (!o || o->kind != Json::Num || !sc || sc->kind != Json::Num)
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.fixedscaleoffset: offset and scale must be numbers"};
+    if (!d || d->kind != Json::Str) throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.fixedscaleoffset: missing dtype"};
+    if (as && as->kind != Json::Str && as->kind != Json::Null)
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.fixedscaleoffset: astype must be a string"};
+    k.fso_offset = (float)o->num;
+    k.fso_scale = (float)sc->num;
+    k.fso_astype = as && as->kind == Json::Str;
+    const std::string dec = numpy_to_v3(d->s), enc = k.fso_astype ? numpy_to_v3(as->s) : dec;
+    if (dec.empty() || enc.empty())
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "numcodecs.fixedscaleoffset: cannot interpret dtype / astype"};
+    k.vt_dec = value_type_of(dt);
+    if (k.vt_dec > VT_F64 || dec != dt)
+      throw ChainError{ZGPU_UNSUPPORTED, "numcodecs.fixedscaleoffset: dtype " + d->s + " on data type " + dt};
+    k.vt_enc = value_type_of(enc);
+    if (k.vt_enc > VT_F64) throw ChainError{ZGPU_UNSUPPORTED, "numcodecs.fixedscaleoffset: astype " + enc};
+    uint8_t ef[16] = {0};
+    fso_encode_element(k, fill, ef);  // encode_fill_value: the fill value through the encoder
+    std::memcpy(T.fill, ef, 16);
+    T.dt = enc;
+    data_type_info(enc, T.es, T.comp);
+    return Role::A2A;
+  }
+  if (k.name == "bitround" || k.name == "numcodecs.bitround" ||
+      k.name == "https://codec.zarrs.dev/array_to_bytes/bitround") {
+    // BitroundCodecConfigurationV1 (numcodecs/bitround.rs:17-22): keepbits (u32), deny_unknown_fields. The
+    // data type stays; the encoded fill value is the rounded fill value (bitround_codec.rs)
+    k.kind = CodecKind::BitRound;
+    if (!cfg || cfg->kind != Json::Obj) throw ChainError{ZGPU_INVALID_ARGUMENT, "bitround: missing configuration"};
+    for (const auto &kv : cfg->obj)
+      if (kv.first != "keepbits") throw ChainError{ZGPU_INVALID_ARGUMENT, "bitround: unknown field '" + kv.first + "'"};
+    const Json *kb = cfg_get("keepbits");
+    if (!kb || kb->kind != Json::Num || !kb->is_int || kb->i < 0 || kb->i > (int64_t)UINT32_MAX)
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "bitround: keepbits must be a non-negative integer"};
+    k.keepbits = (uint32_t)kb->i;
+    k.vt_dec = k.vt_enc = value_type_of(dt);
+    if (k.vt_dec == VT_NONE) throw ChainError{ZGPU_UNSUPPORTED, "bitround: data type " + dt};
+    bitround_element(k.vt_dec, k.keepbits, T.fill);
+    return Role::A2A;
+  }
+  if (k.name == "packbits") {
+    // PackBitsCodecConfigurationV1 (registered/packbits.rs:36-53): padding_encoding?, first_bit?, last_bit?;
+    // deny_unknown_fields. with_context (packbits_codec.rs:152-180) binds the bit range to the data type
+    k.kind = CodecKind::PackBits;
+    if (cfg && cfg->kind != Json::Obj) throw ChainError{ZGPU_INVALID_ARGUMENT, "packbits: bad configuration"};
+    if (cfg)
+      for (const auto &kv : cfg->obj)
+        if (kv.first != "padding_encoding" && kv.first != "first_bit" && kv.first != "last_bit")
+          throw ChainError{ZGPU_INVALID_ARGUMENT, "packbits: unknown field '" + kv.first + "'"};
+    if (const Json *pe = cfg_get("padding_encoding")) {
+      if (pe->kind == Json::Str && pe->s == "first_byte") k.pb_padding = 1;
+      else if (pe->kind == Json::Str && pe->s == "last_byte") k.pb_padding = 2;
+      else if (!(pe->kind == Json::Null || (pe->kind == Json::Str && pe->s == "none")))
+        throw ChainError{ZGPU_INVALID_ARGUMENT, "packbits: padding_encoding must be none, first_byte or last_byte"};
+    }
+    auto bit = [&](const char *key, int64_t def) -> int64_t {
+      const Json *b = cfg_get(key);
+      if (!b || b->kind == Json::Null) return def;
+      if (b->kind != Json::Num || !b->is_int || b->i < 0)
+        throw ChainError{ZGPU_INVALID_ARGUMENT, std::string("packbits: ") + key + " must be a non-negative integer"};
+      return b->i;
+    };
+    // components (zarrs_data_type impl_pack_bits_data_type_traits!): bool is one bit; the complex types
+    // are two float components; only the signed integers sign-extend
+    k.pb_comp_bits = dt == "bool" ? 1 : 8 * comp;
+    k.pb_ncomp = es / comp;
+    k.pb_signed = dt == "int8" || dt == "int16" || dt == "int32" || dt == "int64";
+    const int64_t first = bit("first_bit", 0), last = bit("last_bit", (int64_t)k.pb_comp_bits - 1);
+    if (last < first) throw ChainError{ZGPU_INVALID_ARGUMENT, "packbits: last_bit is less than first_bit"};
+    if (last >= (int64_t)k.pb_comp_bits)
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "packbits: last_bit is outside the data type component"};
+    k.pb_first = (uint32_t)first;
+    k.pb_last = (uint32_t)last;
+    if (k.pb_comp_bits % 8 == 0 && first == 0 && last == (int64_t)k.pb_comp_bits - 1) {
+      // the whole component of a byte-sized type: PackBitsCodecBound encodes and decodes through
+      // BytesCodec(little) and writes no padding byte (packbits_codec.rs:230-240,312-319)
+      k.kind = CodecKind::Bytes;
+      k.big_endian = false;
+    }
+    return Role::A2B;
   }
   if (k.name == "bytes" || k.name == "endian") {  // "endian": legacy alias (array_to_bytes/bytes.rs:53-55)
     k.kind = CodecKind::Bytes;
@@ -89,6 +284,9 @@ static Role create_codec(Codec &k, const Json *cfg, const std::string &dt, uint3
     const Json *ic = cfg_get("codecs");
     if (!ic) throw ChainError{ZGPU_INVALID_ARGUMENT, "sharding: missing codecs"};
     k.inner = parse(*ic, dt, es, comp, fill);
+    if (k.inner->a2b.kind == CodecKind::PackBits)
+      throw ChainError{ZGPU_UNSUPPORTED, "packbits as the array->bytes codec inside sharding_indexed is not supported "
+                                         "by the GPU pipeline (unsharded packbits chains are)"};
     Json defidx = Json::parse(R"([{"name":"bytes","configuration":{"endian":"little"}},{"name":"crc32c"}])");
     const Json *xc = cfg_get("index_codecs");
     const uint8_t ffill[8] = {0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff};
@@ -195,46 +393,67 @@ static std::shared_ptr<Chain> parse(const Json &codecs, const std::string &dt, u
   c->comp = comp;
   c->data_type = dt;
   if (fill) std::memcpy(c->fill, fill, es);
-  bool have_a2b = false;
-  for (const Json &m : codecs.arr) {
+  TypeCtx T{dt, es, comp, {0}};
+  std::memcpy(T.fill, c->fill, 16);
+  struct Entry {
     Codec k;
     const Json *cfg = nullptr;
     bool must_understand = true;
+  };
+  std::vector<Entry> entries;
+  for (const Json &m : codecs.arr) {
+    Entry e;
     if (m.kind == Json::Str) {
-      k.name = m.s;
+      e.k.name = m.s;
     } else if (m.kind == Json::Obj && m.get("name") && m.get("name")->kind == Json::Str) {
       for (const auto &kv : m.obj)
         if (kv.first != "name" && kv.first != "configuration" && kv.first != "must_understand")
           throw ChainError{ZGPU_INVALID_ARGUMENT, "codec metadata: unknown field '" + kv.first + "'"};
-      k.name = m.get("name")->as_str();
-      cfg = m.get("configuration");
+      e.k.name = m.get("name")->as_str();
+      e.cfg = m.get("configuration");
       if (const Json *mu = m.get("must_understand")) {
         if (mu->kind != Json::Bool) throw ChainError{ZGPU_INVALID_ARGUMENT, "must_understand must be a bool"};
-        must_understand = mu->b;
+        e.must_understand = mu->b;
       }
     } else {
       throw ChainError{ZGPU_INVALID_ARGUMENT, "codec metadata must be \"name\" or {name, configuration}"};
     }
-    Role role;
-    try {
-      role = create_codec(k, cfg, dt, es, comp, c->fill);
-    } catch (const ChainError &e) {
-      // zarrs skips an optional codec it cannot create (unknown name or invalid configuration); a
-      // codec zarrs would create but the GPU pipeline lacks stays an error
-      if (must_understand || (e.status == ZGPU_UNSUPPORTED && zarrs_knows(k.name))) throw;
-      continue;
-    }
-    if (role == Role::A2A) {
-      c->a2a.push_back(k);
-    } else if (role == Role::A2B) {
-      if (have_a2b) throw ChainError{ZGPU_INVALID_ARGUMENT, "multiple array to bytes codecs"};
-      c->a2b = k;
-      have_a2b = true;
-    } else {
-      c->b2b.push_back(k);
-    }
+    entries.push_back(e);
   }
+  // the array->array codecs first, in metadata order: each is bound with the data type and fill value
+  // the one before it left (with_context, codec_chain.rs:130-160), the others with the last one's
+  bool have_a2b = false;
+  for (int pass = 0; pass < 2; pass++)
+    for (Entry &e : entries) {
+      if (a2a_name(e.k.name) != (pass == 0)) continue;
+      Codec &k = e.k;
+      Role role;
+      try {
+        role = create_codec(k, e.cfg, T);
+      } catch (const ChainError &err) {
+        // zarrs skips an optional codec it cannot create (unknown name or invalid configuration); a
+        // codec zarrs would create but the GPU pipeline lacks, or cannot bind to this data type, stays
+        // an error
+        if (e.must_understand || (err.status == ZGPU_UNSUPPORTED && (zarrs_knows(k.name) || a2a_name(k.name) ||
+                                                                     k.name == "packbits")))
+          throw;
+        continue;
+      }
+      if (role == Role::A2A) {
+        c->a2a.push_back(k);
+      } else if (role == Role::A2B) {
+        if (have_a2b) throw ChainError{ZGPU_INVALID_ARGUMENT, "multiple array to bytes codecs"};
+        c->a2b = k;
+        have_a2b = true;
+      } else {
+        c->b2b.push_back(k);
+      }
+    }
   if (!have_a2b) throw ChainError{ZGPU_INVALID_ARGUMENT, "missing array to bytes codec"};
+  c->enc_es = T.es;
+  c->enc_comp = T.comp;
+  c->enc_data_type = T.dt;
+  std::memcpy(c->enc_fill, T.fill, 16);
   return c;
 }
 
@@ -245,8 +464,8 @@ std::shared_ptr<Chain> parse_chain(const Json &codecs, const std::string &dt, co
 }
 
 int64_t chain_fixed_encoded_size(const Chain &c, uint64_t nelem) {
-  if (c.a2b.kind != CodecKind::Bytes) return -1;
-  int64_t n = (int64_t)(nelem * c.es);
+  if (c.a2b.kind != CodecKind::Bytes && c.a2b.kind != CodecKind::PackBits) return -1;
+  int64_t n = (int64_t)(c.a2b.kind == CodecKind::PackBits ? packbits_size(c.a2b, nelem) : nelem * c.enc_es);
   for (const Codec &k : c.b2b) {
     if (is_checksum(k.kind)) n += 4;
     else if (k.kind != CodecKind::Shuffle) return -1;
@@ -267,8 +486,8 @@ uint64_t zstd_bound(uint64_t n) { return n + 4 + 14 + 4 + 3 * ((n + 999) / 1000)
 uint64_t bz2_bound(uint64_t n) { return n + n / 8 + 1024; }
 
 int64_t chain_encoded_bound(const Chain &c, uint64_t nelem) {
-  if (c.a2b.kind != CodecKind::Bytes) return -1;
-  uint64_t n = nelem * c.es;
+  if (c.a2b.kind != CodecKind::Bytes && c.a2b.kind != CodecKind::PackBits) return -1;
+  uint64_t n = c.a2b.kind == CodecKind::PackBits ? packbits_size(c.a2b, nelem) : nelem * c.enc_es;
   for (const Codec &k : c.b2b) {
     if (is_checksum(k.kind)) n += 4;
     else if (k.kind == CodecKind::Gzip) n = gzip_bound(n);

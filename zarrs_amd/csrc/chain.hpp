@@ -12,7 +12,8 @@
 
 namespace zgpu {
 
-enum class CodecKind { Transpose, Bytes, Sharding, Crc32c, Gzip, Zstd, Shuffle, Blosc, Zlib, Adler32, Fletcher32, Bz2 };
+enum class CodecKind { Transpose, Bytes, Sharding, Crc32c, Gzip, Zstd, Shuffle, Blosc, Zlib, Adler32, Fletcher32, Bz2,
+                       PackBits, FixedScaleOffset, BitRound };
 
 struct Chain;
 
@@ -30,7 +31,25 @@ struct Codec {
   uint64_t blocksize = 0;             // blosc: 0 = automatic
   std::vector<uint64_t> inner_shape;  // sharding
   std::shared_ptr<Chain> inner, index;
+  // packbits, bound to the data type it encodes (packbits_codec.rs:152-180)
+  uint32_t pb_first = 0, pb_last = 0;      // extracted bit range of a component, inclusive
+  uint32_t pb_comp_bits = 0, pb_ncomp = 0; // component width in bits, components per element
+  bool pb_signed = false;                  // sign extension (signed integers)
+  int pb_padding = 0;                      // padding_encoding: 0 none, 1 first_byte, 2 last_byte
+  // numcodecs.fixedscaleoffset: decoded / encoded element types and whether `astype` was given (the
+  // cast through f32 happens only then); bitround: keepbits over the element type vt_dec
+  float fso_offset = 0, fso_scale = 1;
+  uint32_t vt_dec = 0, vt_enc = 0;  // ZgValueType
+  bool fso_astype = false;
+  uint32_t keepbits = 0;
 };
+
+// Element types of the value codecs (the kernels' template parameter).
+enum ZgValueType : uint32_t { VT_I8, VT_I16, VT_I32, VT_I64, VT_U8, VT_U16, VT_U32, VT_U64, VT_F32, VT_F64,
+                              VT_F16, VT_BF16, VT_NONE };
+ZgValueType value_type_of(const std::string &data_type);
+
+inline bool is_value_codec(CodecKind k) { return k == CodecKind::FixedScaleOffset || k == CodecKind::BitRound; }
 
 struct Chain {
   std::vector<Codec> a2a;
@@ -39,7 +58,22 @@ struct Chain {
   uint32_t es = 0, comp = 0;
   uint8_t fill[16] = {0};
   std::string data_type;
+  // what the array->bytes codec sees: the data type and fill value after the array->array codecs
+  // (equal to the above without a value codec)
+  uint32_t enc_es = 0, enc_comp = 0;
+  uint8_t enc_fill[16] = {0};
+  std::string enc_data_type;
 };
+
+// Whether the chain, or a sharding inner chain below it, holds a value codec.
+bool chain_has_value_codec(const Chain &c);
+// Packed byte length of nelem elements under a packbits codec (PackBitsCodecBound::encode).
+uint64_t packbits_size(const Codec &k, uint64_t nelem);
+// The value codecs' encode of one element on the host (the encoded fill value; the kernels in
+// kernels/value.hip compute the same): out receives the encoded element.
+void fso_encode_element(const Codec &k, const uint8_t *in, uint8_t *out);
+void bitround_element(uint32_t vt, uint32_t keepbits, uint8_t *elem);
+uint32_t value_type_size(uint32_t vt);
 
 struct ChainError {
   int status;

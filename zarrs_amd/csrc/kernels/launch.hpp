@@ -285,6 +285,35 @@ hipError_t launch_shard_encode_var(const uint64_t *starts, const uint8_t *array,
                                    uint64_t *inner_off, uint64_t *index_ptr, uint64_t *shard_len,
                                    uint32_t *shard_status, uint32_t n_shards, hipStream_t s);
 
+// The value codecs and packbits (kernels/value.hip). vt_*: ZgValueType of the encoded / decoded
+// elements, VT_I8..VT_F64; through_f32: `astype` was given, so the cast between the two types runs (through
+// f32, cast_array) even when they are equal; without it they must be equal. in and out hold n elements
+// each and may be the same array only when the element sizes are equal.
+hipError_t launch_fso_decode(uint32_t vt_enc, uint32_t vt_dec, const void *in, void *out, uint64_t n, float offset,
+                             float scale, int through_f32, hipStream_t s);
+hipError_t launch_fso_encode(uint32_t vt_dec, uint32_t vt_enc, const void *in, void *out, uint64_t n, float offset,
+                             float scale, int through_f32, hipStream_t s);
+// bitround encode of n elements of `width` bytes (1, 2, 4, 8); mant: the float type's mantissa bits,
+// 0 for integers
+hipError_t launch_bitround(uint32_t width, uint32_t mant, uint32_t keepbits, const void *in, void *out, uint64_t n,
+                           hipStream_t s);
+struct ZgPackBits {
+  uint64_t nelem;       // elements per chunk
+  uint64_t packed_len;  // encoded bytes per chunk (packbits_size)
+  uint32_t ncomp;       // components per element
+  uint32_t comp_bytes;  // bytes a decoded component takes (1, 2, 4, 8)
+  uint32_t first, ext;  // first extracted bit and number of extracted bits (1..63) of a component
+  uint32_t sign;        // sign-extend (within the byte of the sign bit)
+  uint32_t padding;     // 0 none, 1 first_byte, 2 last_byte
+};
+// tab: n_chunks packed sources | n_chunks destinations (16-byte aligned), on the device. The kernel
+// reads whole aligned dwords: up to 3 bytes either side of a source must be readable. A wrong
+// padding byte sets status[i] = ZG_CORRUPT_STREAM.
+hipError_t launch_unpackbits(const uint64_t *tab, uint32_t *status, uint32_t n_chunks, const ZgPackBits &P,
+                             hipStream_t s);
+// tab: n_chunks sources of native elements | n_chunks destinations of packed_len bytes (any alignment)
+hipError_t launch_packbits(const uint64_t *tab, uint32_t n_chunks, const ZgPackBits &P, hipStream_t s);
+
 // blosc (c-blosc 1.x frames): stream table built on the device, sized on the host from BlInfo (first
 // execution of a plan) or from the capacities that execution recorded (later executions)
 enum : uint32_t { BL_COMP_BLOSCLZ = 0, BL_COMP_LZ4 = 1, BL_COMP_SNAPPY = 2, BL_COMP_ZLIB = 3, BL_COMP_ZSTD = 4, BL_COMP_MEMCPY = 0x100,

@@ -521,6 +521,7 @@ hipStream_t zgpu::ctx_copy_stream(zgpu_ctx *c) {  // nullptr on failure
 static void composed_axes(const Chain &c, uint32_t nd, uint32_t *m) {
   for (uint32_t a = 0; a < nd; a++) m[a] = a;
   for (const Codec &k : c.a2a) {  // E_{k} axis a <-> E_{k-1} axis order[a]
+    if (k.kind != CodecKind::Transpose) continue;  // the value codecs keep every element in its place
     uint32_t t[ZG_MAXD];
     for (uint32_t a = 0; a < nd; a++) t[a] = m[k.order[a]];
     std::memcpy(m, t, nd * sizeof(uint32_t));
@@ -599,6 +600,10 @@ static void plan_build(zgpu_plan &P, const zgpu_chunk_desc *descs) {
   const Chain &top = *P.chain;
   const uint32_t nd = P.nd;
   P.item_desc_status.assign(P.n_desc, 0);
+  if (chain_has_value_codec(top) || top.a2b.kind == CodecKind::PackBits)
+    throw ChainError{ZGPU_UNSUPPORTED, "chains with numcodecs.fixedscaleoffset, bitround or packbits do not take the "
+                                       "fused plan (zgpu_plan_create, zgpu_group_create): decode them through "
+                                       "zgpu_decode_batch / zgpu_decode_into / zgpu_decode_pinned"};
   const bool shard_chain = top.a2b.kind == CodecKind::Sharding;
   // transpose codecs before sharding_indexed (codec_chain.rs:557-646: the sharding codec decodes the
   // transposed array): the shard and its inner chunk grid live in the encoded frame, encoded axis a
@@ -609,7 +614,7 @@ static void plan_build(zgpu_plan &P, const zgpu_chunk_desc *descs) {
   bool outer_perm = false;
   if (shard_chain) {
     for (const Codec &k : top.a2a)
-      if (k.order.size() != nd) throw ChainError{ZGPU_INVALID_ARGUMENT, "transpose order rank != array rank"};
+      if (k.kind == CodecKind::Transpose && k.order.size() != nd) throw ChainError{ZGPU_INVALID_ARGUMENT, "transpose order rank != array rank"};
     composed_axes(top, nd, mo);
     for (uint32_t a = 0; a < nd; a++) outer_perm = outer_perm || mo[a] != a;
     if (!top.b2b.empty()) throw ChainError{ZGPU_UNSUPPORTED, "bytes->bytes codecs after sharding_indexed"};
@@ -632,7 +637,7 @@ static void plan_build(zgpu_plan &P, const zgpu_chunk_desc *descs) {
   P.sharded = shard_chain;
   P.nested = mid != nullptr;
   for (const Codec &k : leaf.a2a)
-    if (k.order.size() != nd) throw ChainError{ZGPU_INVALID_ARGUMENT, "transpose order rank != array rank"};
+    if (k.kind == CodecKind::Transpose && k.order.size() != nd) throw ChainError{ZGPU_INVALID_ARGUMENT, "transpose order rank != array rank"};
 
   // leaf chunk shape
   uint64_t leaf_shape[ZG_MAXD];
@@ -1418,6 +1423,7 @@ static Lane *plan_lane(zgpu_plan &P) {
 // Synchronous (per-stage read-backs); per-descriptor statuses, first failing item of a descriptor.
 // ------------------------------------------------------------------------------------------------
 static bool fused_plannable(const Chain &top) {
+  if (chain_has_value_codec(top) || top.a2b.kind == CodecKind::PackBits) return false;
   if (top.a2b.kind != CodecKind::Sharding) return true;
   if (!top.b2b.empty()) return false;
   const Chain &mid = *top.a2b.inner;
@@ -1883,6 +1889,326 @@ static void transposed_general(GeneralCall &G, const std::shared_ptr<Chain> &cha
   G.C->dev_free(Pk);
 }
 
+// The chain without its value codecs (numcodecs.fixedscaleoffset, bitround), at every sharding level;
+// `steps` receives them in encode order. They work element by element, so they commute with
+// chunking, sharding, transposes and selection: what the stripped chain decodes, in the innermost
+// encoded data type, is the selection before the value codecs' decode.
+static std::shared_ptr<Chain> strip_value_codecs(const Chain &c, std::vector<Codec> &steps) {
+  auto r = std::make_shared<Chain>(c);
+  r->a2a.clear();
+  for (const Codec &k : c.a2a) {
+    if (is_value_codec(k.kind)) steps.push_back(k);
+    else r->a2a.push_back(k);
+  }
+  if (c.a2b.kind == CodecKind::Sharding) r->a2b.inner = strip_value_codecs(*c.a2b.inner, steps);
+  return r;
+}
+
+// Every level of a stripped chain bound to the innermost encoded data type and fill value.
+static void retype_stripped(Chain &c, const Chain &original) {
+  const Chain *leaf = &original;
+  while (leaf->a2b.kind == CodecKind::Sharding) leaf = leaf->a2b.inner.get();
+  for (Chain *l = &c;; l = l->a2b.inner.get()) {
+    l->es = l->enc_es = leaf->enc_es;
+    l->comp = l->enc_comp = leaf->enc_comp;
+    l->data_type = l->enc_data_type = leaf->enc_data_type;
+    std::memcpy(l->fill, leaf->enc_fill, 16);
+    std::memcpy(l->enc_fill, leaf->enc_fill, 16);
+    if (l->a2b.kind != CodecKind::Sharding) break;
+  }
+}
+
+static uint32_t mantissa_bits_of(uint32_t vt) {
+  return vt == VT_F16 ? 10 : vt == VT_BF16 ? 7 : vt == VT_F32 ? 23 : vt == VT_F64 ? 52 : 0;
+}
+
+// n elements through the value codecs' decode (`steps` in encode order, run backwards) from `in`, in
+// the innermost encoded type, into `out` (must not be `in`), in the decoded type. bitround decodes
+// as the identity. Temporaries go to `owned`. Enqueues only.
+static void value_decode_elements(zgpu_ctx *C, const std::vector<Codec> &steps, const uint8_t *in, uint8_t *out,
+                                  uint64_t n, uint32_t es_out, std::vector<void *> &owned, hipStream_t s) {
+  std::vector<const Codec *> fso;
+  for (size_t j = steps.size(); j-- > 0;)
+    if (steps[j].kind == CodecKind::FixedScaleOffset) fso.push_back(&steps[j]);
+  if (fso.empty()) {
+    if (n) HIPCHK(hipMemcpyAsync(out, in, n * es_out, hipMemcpyDeviceToDevice, s));
+    return;
+  }
+  const uint8_t *cur = in;
+  for (size_t j = 0; j < fso.size(); j++) {
+    const Codec &k = *fso[j];
+    uint8_t *dst = out;
+    if (j + 1 < fso.size()) {
+      dst = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n * value_type_size(k.vt_dec), 1));
+      owned.push_back(dst);
+    }
+    HIPCHK(launch_fso_decode(k.vt_enc, k.vt_dec, cur, dst, n, k.fso_offset, k.fso_scale, k.fso_astype ? 1 : 0, s));
+    cur = dst;
+  }
+}
+
+// n elements through the value codecs' encode, `in` (decoded type) to a new device array in the
+// innermost encoded type (returned, in `owned`).
+static uint8_t *value_encode_elements(zgpu_ctx *C, const std::vector<Codec> &steps, const uint8_t *in, uint64_t n,
+                                      std::vector<void *> &owned, hipStream_t s) {
+  const uint8_t *cur = in;
+  uint8_t *dst = nullptr;
+  for (const Codec &k : steps) {
+    dst = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n * value_type_size(k.vt_enc), 1));
+    owned.push_back(dst);
+    if (k.kind == CodecKind::FixedScaleOffset)
+      HIPCHK(launch_fso_encode(k.vt_dec, k.vt_enc, cur, dst, n, k.fso_offset, k.fso_scale, k.fso_astype ? 1 : 0, s));
+    else
+      HIPCHK(launch_bitround(value_type_size(k.vt_dec), mantissa_bits_of(k.vt_dec), k.keepbits, cur, dst, n, s));
+    cur = dst;
+  }
+  return dst;
+}
+
+// Chains with value codecs, before sharding_indexed, inside its inner chains, or both. The chain
+// without them, retyped to the innermost encoded data type and fill value, decodes the callers'
+// selections into a device buffer of that type (so a missing chunk or inner chunk holds the encoded
+// fill value, as in zarrs); k_fso_decode then converts the buffer into the output: one extra pass over
+// the data when the descriptors cover the output (the converted buffer is the output), and through the
+// stacked boxes of transposed_general otherwise. Only bitround: its decode is the identity, so the
+// stripped chain writes the output itself.
+static void value_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
+                          uint64_t n, int32_t *status) {
+  const Chain &top = *chain;
+  const uint32_t nd = G.nd;
+  std::vector<Codec> steps;
+  auto bare = strip_value_codecs(top, steps);
+  retype_stripped(*bare, top);
+  bool any_fso = false;
+  for (const Codec &k : steps) any_fso = any_fso || k.kind == CodecKind::FixedScaleOffset;
+  if (!any_fso) {
+    decode_general(G, bare, descs, n, status);
+    return;
+  }
+  const uint32_t es_e = bare->es, es_d = top.es;
+  std::vector<void *> owned;
+  auto release = [&]() {
+    (void)hipStreamSynchronize(G.s);
+    for (void *p : owned) G.C->dev_free(p);
+    owned.clear();
+  };
+  try {
+    bool geometry = true;
+    uint64_t covered = 0, out_elems = 1;
+    for (uint64_t i = 0; i < n; i++) {
+      geometry = geometry && desc_geometry_ok(descs[i], nd, G.out_shape);
+      covered += sel_volume(descs[i], nd);
+    }
+    for (uint32_t d = 0; d < nd; d++) out_elems *= G.out_shape[d];
+    if (geometry && covered == out_elems) {
+      // the (disjoint) selections tile the output: decode into its image in the encoded type, convert
+      uint8_t *T = (uint8_t *)G.C->dev_alloc(std::max<uint64_t>(out_elems * es_e, 1));
+      owned.push_back(T);
+      GeneralCall G1{G.C, G.validate, nd, T, G.out_shape, G.flags, G.s, {}};
+      decode_general(G1, bare, descs, n, status);
+      value_decode_elements(G.C, steps, T, G.out, out_elems, es_d, owned, G.s);
+      release();
+      return;
+    }
+    // every selection into its own box of a stacked buffer, packed compact, converted, then scattered
+    // as the leaf chunks of [bytes(native)] in the decoded type
+    auto plain = std::make_shared<Chain>(top);
+    plain->a2a.clear();
+    plain->b2b.clear();
+    plain->a2b = Codec{};
+    plain->a2b.kind = CodecKind::Bytes;
+    plain->a2b.name = "bytes";
+    plain->enc_es = top.es;
+    plain->enc_comp = top.comp;
+    plain->enc_data_type = top.data_type;
+    std::memcpy(plain->enc_fill, top.fill, 16);
+    std::vector<zgpu_chunk_desc> enc_descs;
+    std::vector<uint64_t> owner, row0;
+    uint64_t stacked[ZG_MAXD] = {0};
+    for (uint64_t i = 0; i < n; i++) {
+      const zgpu_chunk_desc &D = descs[i];
+      if (!desc_geometry_ok(D, nd, G.out_shape)) {
+        status[i] = ZGPU_INVALID_ARGUMENT;
+        continue;
+      }
+      if (sel_volume(D, nd) == 0) continue;
+      zgpu_chunk_desc E = D;
+      for (uint32_t a = 0; a < nd; a++) E.out_start[a] = 0;
+      E.out_start[0] = stacked[0];
+      row0.push_back(stacked[0]);
+      stacked[0] += E.sel_shape[0];
+      for (uint32_t a = 1; a < nd; a++) stacked[a] = std::max(stacked[a], E.sel_shape[a]);
+      enc_descs.push_back(E);
+      owner.push_back(i);
+    }
+    if (enc_descs.empty()) return;
+    uint64_t stacked_elems = 1, pack_elems = 0;
+    for (uint32_t a = 0; a < nd; a++) stacked_elems *= stacked[a];
+    std::vector<uint64_t> pack_off(enc_descs.size());
+    for (size_t k = 0; k < enc_descs.size(); k++) {
+      pack_off[k] = pack_elems;
+      pack_elems += sel_volume(enc_descs[k], nd);
+    }
+    uint8_t *T = (uint8_t *)G.C->dev_alloc(stacked_elems * es_e);
+    owned.push_back(T);
+    GeneralCall G1{G.C, G.validate, nd, T, stacked, G.flags, G.s, {}};
+    std::vector<int32_t> st(enc_descs.size(), 0);
+    const bool had_detail = g_size_detail.valid;
+    decode_general(G1, bare, enc_descs.data(), enc_descs.size(), st.data());
+    if (!had_detail && g_size_detail.valid) g_size_detail.desc = owner[g_size_detail.desc];
+    uint8_t *PkE = (uint8_t *)G.C->dev_alloc(pack_elems * es_e);
+    owned.push_back(PkE);
+    uint8_t *PkD = (uint8_t *)G.C->dev_alloc(pack_elems * es_d);
+    owned.push_back(PkD);
+    std::vector<zgpu_chunk_desc> leaf;
+    std::vector<uint64_t> leaf_owner;
+    for (size_t k = 0; k < enc_descs.size(); k++) {
+      const uint64_t i = owner[k];
+      if (st[k]) {
+        status[i] = st[k];
+        continue;
+      }
+      uint64_t org[ZG_MAXD] = {0};
+      org[0] = row0[k];
+      pack_box(T, nd, stacked, org, enc_descs[k].sel_shape, es_e, PkE, pack_off[k] * es_e, G.s);
+      zgpu_chunk_desc L{};
+      L.enc = PkD + pack_off[k] * es_d;
+      L.enc_len = sel_volume(enc_descs[k], nd) * es_d;
+      for (uint32_t a = 0; a < nd; a++) {
+        L.chunk_shape[a] = L.sel_shape[a] = descs[i].sel_shape[a];
+        L.sel_start[a] = 0;
+        L.out_start[a] = descs[i].out_start[a];
+      }
+      leaf.push_back(L);
+      leaf_owner.push_back(i);
+    }
+    value_decode_elements(G.C, steps, PkE, PkD, pack_elems, es_d, owned, G.s);
+    run_sub(G, plain, leaf, leaf_owner, status);
+  } catch (...) {
+    release();
+    throw;
+  }
+  release();
+}
+
+// packbits as the array->bytes codec (unsharded): its chunks are not element-aligned, so whole chunks
+// of [bytes(uint8), bytes->bytes codecs...] over the packed length are decoded into a device buffer
+// (which checks the packed length: DECODED_SIZE_MISMATCH), k_unpackbits expands them into native
+// elements (and checks the padding byte: CORRUPT_STREAM), and those are the leaf chunks of
+// [array->array codecs..., bytes(native)] with the callers' selections.
+static void packbits_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
+                             uint64_t n, int32_t *status) {
+  const Chain &top = *chain;
+  const Codec &pb = top.a2b;
+  const uint32_t nd = G.nd, es = top.enc_es;
+  uint64_t nelem = 1;
+  for (uint32_t d = 0; d < nd; d++) nelem *= descs[0].chunk_shape[d];
+  const uint64_t packed = packbits_size(pb, nelem);
+  const uint64_t ppitch = ((packed + 15) & ~(uint64_t)15) + 16, upitch = (nelem * es + 15) & ~(uint64_t)15;
+  auto packed_chain = std::make_shared<Chain>();
+  packed_chain->es = packed_chain->comp = packed_chain->enc_es = packed_chain->enc_comp = 1;
+  packed_chain->data_type = packed_chain->enc_data_type = "uint8";
+  packed_chain->a2b.kind = CodecKind::Bytes;
+  packed_chain->a2b.name = "bytes";
+  packed_chain->b2b = top.b2b;
+  auto leaf_chain = std::make_shared<Chain>(top);
+  leaf_chain->b2b.clear();
+  leaf_chain->a2b = Codec{};
+  leaf_chain->a2b.kind = CodecKind::Bytes;
+  leaf_chain->a2b.name = "bytes";
+  std::vector<zgpu_chunk_desc> pk;  // 1-D descriptors of the packed chunks, slot j of the buffer
+  std::vector<uint64_t> pk_owner;
+  for (uint64_t i = 0; i < n; i++) {
+    const zgpu_chunk_desc &D = descs[i];
+    if (!desc_geometry_ok(D, nd, G.out_shape)) {
+      status[i] = ZGPU_INVALID_ARGUMENT;
+      continue;
+    }
+    if (!D.enc || sel_volume(D, nd) == 0) continue;  // a missing chunk: the leaf chain fills it
+    zgpu_chunk_desc E{};
+    E.enc = D.enc;
+    E.enc_len = D.enc_len;
+    E.chunk_shape[0] = E.sel_shape[0] = packed;
+    E.out_start[0] = pk.size() * ppitch;
+    pk.push_back(E);
+    pk_owner.push_back(i);
+  }
+  const uint64_t m = pk.size();
+  uint8_t *B = nullptr, *U = nullptr;
+  uint64_t *d_tab = nullptr;
+  uint32_t *d_st = nullptr;
+  auto release = [&]() {
+    (void)hipStreamSynchronize(G.s);
+    G.C->dev_free(B);
+    G.C->dev_free(U);
+    G.C->dev_free(d_tab);
+    G.C->dev_free(d_st);
+  };
+  try {
+    std::vector<int32_t> st(m, 0);
+    std::vector<uint64_t> slot(n, UINT64_MAX);
+    if (m) {
+      const uint64_t b_shape[1] = {m * ppitch};
+      B = (uint8_t *)G.C->dev_alloc(m * ppitch);
+      U = (uint8_t *)G.C->dev_alloc(std::max<uint64_t>(m * upitch, 1));
+      GeneralCall G1{G.C, G.validate, 1, B, b_shape, G.flags, G.s, {}};
+      const bool had_detail = g_size_detail.valid;
+      decode_general(G1, packed_chain, pk.data(), m, st.data());
+      if (!had_detail && g_size_detail.valid) g_size_detail.desc = pk_owner[g_size_detail.desc];
+      std::vector<uint64_t> tab;
+      std::vector<uint64_t> ok;
+      for (uint64_t j = 0; j < m; j++)
+        if (!st[j]) ok.push_back(j);
+      for (uint64_t j : ok) tab.push_back((uint64_t)(B + j * ppitch));
+      for (uint64_t j : ok) tab.push_back((uint64_t)(U + j * upitch));
+      if (!ok.empty()) {
+        d_tab = (uint64_t *)G.C->dev_alloc(tab.size() * 8);
+        d_st = (uint32_t *)G.C->dev_alloc(ok.size() * 4);
+        HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, G.s));
+        HIPCHK(hipMemsetAsync(d_st, 0, ok.size() * 4, G.s));
+        ZgPackBits P{};
+        P.nelem = nelem;
+        P.packed_len = packed;
+        P.ncomp = pb.pb_ncomp;
+        P.comp_bytes = es / pb.pb_ncomp;
+        P.first = pb.pb_first;
+        P.ext = pb.pb_last - pb.pb_first + 1;
+        P.sign = pb.pb_signed ? 1 : 0;
+        P.padding = (uint32_t)pb.pb_padding;
+        HIPCHK(launch_unpackbits(d_tab, d_st, (uint32_t)ok.size(), P, G.s));
+        std::vector<uint32_t> ust(ok.size());
+        HIPCHK(hipMemcpyAsync(ust.data(), d_st, ok.size() * 4, hipMemcpyDeviceToHost, G.s));
+        HIPCHK(hipStreamSynchronize(G.s));
+        for (size_t k = 0; k < ok.size(); k++) st[ok[k]] = (int32_t)ust[k];
+      }
+      for (uint64_t j = 0; j < m; j++) {
+        if (st[j]) status[pk_owner[j]] = st[j];
+        else slot[pk_owner[j]] = j;
+      }
+    }
+    std::vector<zgpu_chunk_desc> leaf;
+    std::vector<uint64_t> leaf_owner;
+    for (uint64_t i = 0; i < n; i++) {
+      if (status[i] || sel_volume(descs[i], nd) == 0) continue;
+      zgpu_chunk_desc L = descs[i];
+      if (slot[i] != UINT64_MAX) {
+        L.enc = U + slot[i] * upitch;
+        L.enc_len = nelem * es;
+      } else {
+        L.enc = nullptr;
+        L.enc_len = 0;
+      }
+      leaf.push_back(L);
+      leaf_owner.push_back(i);
+    }
+    run_sub(G, leaf_chain, leaf, leaf_owner, status);
+  } catch (...) {
+    release();
+    throw;
+  }
+  release();
+}
+
 static void decode_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
                            uint64_t n, int32_t *status) {
   for (uint64_t i = 0; i < n; i++) status[i] = 0;
@@ -1903,6 +2229,12 @@ static void decode_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, 
     return;
   }
   const Chain &top = *chain;
+  if (chain_has_value_codec(top) || top.a2b.kind == CodecKind::PackBits) {
+    if (!n) return;
+    if (chain_has_value_codec(top)) value_general(G, chain, descs, n, status);
+    else packbits_general(G, chain, descs, n, status);
+    return;
+  }
   if (fused_plannable(top)) {
     std::unique_ptr<zgpu_plan> P(plan_new(G.C, chain, G.validate, G.nd, descs, n, G.out_shape, G.flags));
     plan_upload(*P, G.s);
@@ -3200,7 +3532,9 @@ int64_t zgpu_chain_encoded_bound(const zgpu_chain *ch, uint32_t nd, const uint64
     for (uint32_t d = 0; d < nd; d++) n *= chunk_shape[d];
     return chain_encoded_bound(c, n);
   }
-  if (!c.a2a.empty() || !c.b2b.empty() || c.a2b.inner_shape.size() != nd) return -1;
+  for (const Codec &k : c.a2a)
+    if (!is_value_codec(k.kind)) return -1;  // (value codecs keep the shape; encode strips them)
+  if (!c.b2b.empty() || c.a2b.inner_shape.size() != nd) return -1;
   uint64_t n_inner = 1, inner_n = 1;
   for (uint32_t d = 0; d < nd; d++) {
     const uint64_t is = c.a2b.inner_shape[d];
@@ -3270,7 +3604,7 @@ static int encode_fixed(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t
                         std::vector<void *> &owned, hipStream_t s, ZgEncode *out_P = nullptr) {
   if (c.a2b.kind != CodecKind::Bytes) return set_err(ZGPU_UNSUPPORTED, "encode: array->bytes codec must be bytes");
   for (const Codec &k : c.a2a)
-    if (k.order.size() != nd) return set_err(ZGPU_INVALID_ARGUMENT, "transpose order rank != ndim");
+    if (k.kind == CodecKind::Transpose && k.order.size() != nd) return set_err(ZGPU_INVALID_ARGUMENT, "transpose order rank != ndim");
   bool shuffle = false;
   int n_start = 0;
   for (size_t i = 0; i < c.b2b.size(); i++) {
@@ -3326,7 +3660,7 @@ static int encode_var(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t *
                       ZgEncode *P_out) {
   if (c.a2b.kind != CodecKind::Bytes) return set_err(ZGPU_UNSUPPORTED, "encode: array->bytes codec must be bytes");
   for (const Codec &k : c.a2a)
-    if (k.order.size() != nd) return set_err(ZGPU_INVALID_ARGUMENT, "transpose order rank != ndim");
+    if (k.kind == CodecKind::Transpose && k.order.size() != nd) return set_err(ZGPU_INVALID_ARGUMENT, "transpose order rank != ndim");
   uint64_t nelem = 1;
   for (uint32_t d = 0; d < nd; d++) nelem *= chunk_shape[d];
   bool shuffle = false;
@@ -3626,6 +3960,83 @@ static int encode_sharded(zgpu_ctx *C, const Chain &top, uint32_t nd, const uint
   return ZGPU_OK;
 }
 
+// packbits as the array->bytes codec (unsharded): the chunks are gathered (and transposed) as native
+// elements into temporary slots, k_packbits packs each slot, and the packed chunks, a 1-D uint8 array
+// of one slot per chunk, go through [bytes(uint8), bytes->bytes codecs...] to their destinations
+// (straight into them without bytes->bytes codecs).
+static int encode_packbits(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t *chunk_shape, const void *array,
+                           const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint64_t *enc_lens,
+                           std::vector<void *> &owned, hipStream_t s) {
+  const Codec &pb = c.a2b;
+  const uint32_t es = c.enc_es;
+  const uint64_t nelem = volume(chunk_shape, nd), packed = packbits_size(pb, nelem);
+  const uint64_t upitch = (nelem * es + 15) & ~(uint64_t)15, ppitch = (packed + 15) & ~(uint64_t)15;
+  Chain native = c;  // [array->array codecs..., bytes(native)]
+  native.b2b.clear();
+  native.a2b = Codec{};
+  native.a2b.kind = CodecKind::Bytes;
+  native.a2b.name = "bytes";
+  Chain packed_chain;  // [bytes(uint8), bytes->bytes codecs...]
+  packed_chain.es = packed_chain.comp = packed_chain.enc_es = packed_chain.enc_comp = 1;
+  packed_chain.data_type = packed_chain.enc_data_type = "uint8";
+  packed_chain.a2b = native.a2b;
+  packed_chain.b2b = c.b2b;
+  const bool direct = c.b2b.empty();
+  const int64_t bound = direct ? (int64_t)packed : chain_encoded_bound(packed_chain, packed);
+  if (bound < 0) return set_err(ZGPU_UNSUPPORTED, "encode: the chain's encoded size is not bounded");
+  for (uint64_t i = 0; i < n; i++)
+    if (!descs[i].dst || descs[i].dst_cap < (uint64_t)bound)
+      return set_err(ZGPU_INVALID_ARGUMENT, "encode: destination missing or smaller than the encoded bound");
+  uint8_t *U = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n * upitch, 1));
+  owned.push_back(U);
+  uint8_t *Pk = nullptr;
+  if (!direct) {
+    Pk = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n * ppitch, 1));
+    owned.push_back(Pk);
+  }
+  std::vector<uint64_t> tab(n * (1 + nd)), ptab(2 * n);
+  for (uint64_t i = 0; i < n; i++) {
+    tab[i] = ptab[i] = (uint64_t)(U + i * upitch);
+    for (uint32_t d = 0; d < nd; d++) tab[n + i * nd + d] = descs[i].chunk_start[d];
+    ptab[n + i] = direct ? (uint64_t)descs[i].dst : (uint64_t)(Pk + i * ppitch);
+  }
+  int rc = encode_fixed(C, native, nd, chunk_shape, array, array_shape, tab, n, owned, s);
+  if (rc) return rc;
+  uint64_t *d_ptab = (uint64_t *)C->dev_alloc(ptab.size() * 8);
+  owned.push_back(d_ptab);
+  HIPCHK(hipMemcpyAsync(d_ptab, ptab.data(), ptab.size() * 8, hipMemcpyHostToDevice, s));
+  ZgPackBits P{};
+  P.nelem = nelem;
+  P.packed_len = packed;
+  P.ncomp = pb.pb_ncomp;
+  P.comp_bytes = es / pb.pb_ncomp;
+  P.first = pb.pb_first;
+  P.ext = pb.pb_last - pb.pb_first + 1;
+  P.sign = pb.pb_signed ? 1 : 0;
+  P.padding = (uint32_t)pb.pb_padding;
+  HIPCHK(launch_packbits(d_ptab, (uint32_t)n, P, s));
+  if (direct) {
+    HIPCHK(hipStreamSynchronize(s));  // ptab is read by the copy above
+    for (uint64_t i = 0; i < n; i++) enc_lens[i] = packed;
+    return ZGPU_OK;
+  }
+  // the packed chunks as chunk i = [i * ppitch, i * ppitch + packed) of a 1-D uint8 array
+  const uint64_t p_shape[1] = {n * ppitch}, p_chunk[1] = {packed};
+  std::vector<zgpu_encode_desc> pd(descs, descs + n);
+  for (uint64_t i = 0; i < n; i++) pd[i].chunk_start[0] = i * ppitch;
+  if (chain_compresses(packed_chain))
+    return encode_compressed(C, packed_chain, 1, p_chunk, Pk, p_shape, pd.data(), n, enc_lens, owned, s);
+  std::vector<uint64_t> t2(2 * n);
+  for (uint64_t i = 0; i < n; i++) {
+    t2[i] = (uint64_t)descs[i].dst;
+    t2[n + i] = i * ppitch;
+  }
+  rc = encode_fixed(C, packed_chain, 1, p_chunk, Pk, p_shape, t2, n, owned, s);
+  HIPCHK(hipStreamSynchronize(s));  // the tables are read by encode_fixed's copies
+  for (uint64_t i = 0; i < n; i++) enc_lens[i] = (uint64_t)bound;
+  return rc;
+}
+
 extern "C" {
 
 int zgpu_encode_chunks(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, const void *array,
@@ -3637,7 +4048,6 @@ int zgpu_encode_chunks(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape,
   if (nd == 0 || nd > ZGPU_MAX_DIMS) return set_err(ZGPU_INVALID_ARGUMENT, "ndim out of range");
   if ((flags & (ZGPU_ENC_DEVICE | ZGPU_OUT_DEVICE)) != (ZGPU_ENC_DEVICE | ZGPU_OUT_DEVICE))
     return set_err(ZGPU_INVALID_ARGUMENT, "encode: array and destinations must be device memory");
-  const Chain &c = *ch->chain;
   for (uint64_t i = 0; i < n; i++)
     for (uint32_t d = 0; d < nd; d++)
       if (descs[i].chunk_start[d] >= array_shape[d])
@@ -3650,7 +4060,24 @@ int zgpu_encode_chunks(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape,
   std::vector<void *> owned;
   int rc = 0;
   try {
-    if (c.a2b.kind == CodecKind::Sharding) {
+    // value codecs (numcodecs.fixedscaleoffset, bitround) work element by element, so they commute with
+    // chunking and sharding: the caller's array is converted once into a device array of the innermost
+    // encoded type, which the chain without them, retyped, encodes (strip_value_codecs)
+    std::shared_ptr<Chain> stripped;
+    if (chain_has_value_codec(*ch->chain)) {
+      std::vector<Codec> steps;
+      stripped = strip_value_codecs(*ch->chain, steps);
+      retype_stripped(*stripped, *ch->chain);
+      array = value_encode_elements(C, steps, (const uint8_t *)array, volume(array_shape, nd), owned, s);
+    }
+    const Chain &c = stripped ? *stripped : *ch->chain;
+    if (c.a2b.kind == CodecKind::PackBits) {
+      uint64_t *hl = (uint64_t *)C->host_alloc(8 * n);
+      rc = encode_packbits(C, c, nd, chunk_shape, array, array_shape, descs, n, hl, owned, s);
+      HIPCHK(hipStreamSynchronize(s));
+      if (!rc && enc_lens) std::memcpy(enc_lens, hl, 8 * n);
+      C->host_free(hl);
+    } else if (c.a2b.kind == CodecKind::Sharding) {
       uint64_t *hl = (uint64_t *)C->host_alloc(8 * n);
       rc = encode_sharded(C, c, nd, chunk_shape, array, array_shape, descs, n, hl, owned, s);
       HIPCHK(hipStreamSynchronize(s));
