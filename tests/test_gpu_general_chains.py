@@ -2,7 +2,7 @@
 bytes->bytes codecs after sharding_indexed (a checksum / compressor over the whole shard), sharding
 nested three deep, codecs around a nested sharding_indexed, and batches mixing chunk shapes.
 zarrs composes any chain (codec_chain.rs:192-229) and decodes each chunk with its own shape;
-libzgpu composes them from fused plans (zgpu.cpp decode_general)."""
+libzgpu composes them from fused plans (general.cpp decode_general)."""
 import numpy as np
 import pytest
 
@@ -33,7 +33,7 @@ CHAINS = {
     "around_nested": [sh([8, 16, 16], [{"name": "transpose", "configuration": {"order": [2, 1, 0]}},
                                         sh([4, 8, 8], LEAF), {"name": "crc32c"}])],
     # transposes before a sharding the fused plan does not take: decoded in the encoded frame, then
-    # transposed and scattered (zgpu.cpp transposed_general)
+    # transposed and scattered (general.cpp transposed_general)
     "transpose_nested_zstd": [{"name": "transpose", "configuration": {"order": [2, 1, 0]}},
                               sh([8, 16, 8], [sh([4, 8, 4], LEAF)]),
                               {"name": "zstd", "configuration": {"level": 3, "checksum": False}}],

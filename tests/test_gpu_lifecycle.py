@@ -171,3 +171,202 @@ def test_pinned_calls_keep_pools_bounded(monkeypatch):
     assert s["dev_free"] == 0 and s["host_free"] == 0, s
     del chain
     ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------
+# Call-scoped memory: the composed ("general") decode paths and the write path take their temporaries
+# from the context's pools through one scoped owner (csrc/ctx.hpp Scratch), so a call leaves the pools'
+# in-use level where it found it, whether it succeeds or a descriptor fails.
+# ---------------------------------------------------------------------------------------------------
+import value_codecs as V  # noqa: E402  (the numpy model of packbits / fixedscaleoffset, a helper module)
+
+# The chains, the [16, 32, 32] array and the sub-selection are those of tests/test_gpu_general_chains.py
+# (shard_crc_zstd, deep3, transpose_nested_zstd) and tests/test_gpu_value_codecs.py (fixedscaleoffset
+# f32 -> u8 before a shard, packbits of bool), restated here so that the test files stay independent.
+SHAPE = [16, 32, 32]
+PARTIAL = ([3, 5, 7], [11, 20, 22])
+WHOLE = ([0, 0, 0], SHAPE)
+BYTES = {"name": "bytes", "configuration": {"endian": "little"}}
+GZIP = {"name": "gzip", "configuration": {"level": 1}}
+ZSTD = {"name": "zstd", "configuration": {"level": 3, "checksum": True}}
+CRC = {"name": "crc32c"}
+
+
+def sh(cs, inner, loc="end"):
+    return {"name": "sharding_indexed",
+            "configuration": {"chunk_shape": cs, "codecs": inner, "index_codecs": [BYTES, CRC], "index_location": loc}}
+
+
+def packbits(first=None, last=None, padding="none"):
+    cfg = {"padding_encoding": padding}
+    if first is not None:
+        cfg["first_bit"], cfg["last_bit"] = first, last
+    return {"name": "packbits", "configuration": cfg}
+
+
+FSO = {"name": V.FSO, "configuration": {"offset": 1000, "scale": 10, "dtype": "f4", "astype": "u1"}}
+CHAINS = {
+    "shard_crc_zstd": [sh([4, 8, 8], [BYTES, GZIP]), CRC, ZSTD],
+    "deep3": [sh([8, 16, 16], [sh([4, 8, 8], [sh([2, 4, 4], [BYTES, GZIP])])])],
+    "transpose_nested_zstd": [{"name": "transpose", "configuration": {"order": [2, 1, 0]}},
+                              sh([8, 16, 8], [sh([4, 8, 4], [BYTES, GZIP])]),
+                              {"name": "zstd", "configuration": {"level": 3, "checksum": False}}],
+}
+FSO_CODECS = [FSO, sh([4, 8, 8], [BYTES, GZIP])]
+PACKBITS_CODECS = [packbits(padding="last_byte")]
+
+
+def _general_array(seed, fill):
+    """as tests/test_gpu_general_chains.py: rounded normals with two all-fill regions (omitted inner chunks)"""
+    a = np.round(np.random.default_rng(seed).standard_normal(SHAPE) * 20 + (fill if fill > 100 else 0)).astype(np.float32)
+    a[8:16, 0:16, 16:32] = fill
+    a[0:2, 0:4, 0:4] = fill
+    return a
+
+
+def _tensor(torch, a):
+    """a device tensor holding a's bytes (torch has no unsigned 16-bit element type)"""
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy((a.view("<i2") if a.dtype == np.uint16 else a).copy()).cuda()
+
+
+# name -> (codecs, data type, fill, selections, byte to flip, xor mask, status of the flipped stream)
+# The flipped byte is one every read of the chunk goes through, whatever its selection: the zstd frame's
+# content checksum, the outer shard index's crc32c, the zstd magic number, the packbits padding byte.
+DECODE_CASES = {
+    "shard_crc_zstd": (CHAINS["shard_crc_zstd"], "float32", 3, [PARTIAL], -1, 0xFF, "CORRUPT_STREAM"),
+    "deep3": (CHAINS["deep3"], "float32", 3, [PARTIAL], -1, 0xFF, "INVALID_CHECKSUM"),
+    "transpose_nested_zstd": (CHAINS["transpose_nested_zstd"], "float32", 3, [PARTIAL], 0, 0xFF, "CORRUPT_STREAM"),
+    # value_general: descriptors that tile the output, then a partial selection (the stacked boxes)
+    "fixedscaleoffset": (FSO_CODECS, "float32", 1001.23, [WHOLE, PARTIAL], -1, 0xFF, "INVALID_CHECKSUM"),
+    "packbits_bool": (PACKBITS_CODECS, "bool", 0, [PARTIAL], -1, 0x02, "CORRUPT_STREAM"),
+}
+
+
+def _decode_case(name):
+    """(array, encoded, expected decode, flipped stream): the models run once per case"""
+    codecs, dt, fill, _, pos, mask, _ = DECODE_CASES[name]
+    if name == "packbits_bool":
+        a = np.random.default_rng(17).integers(0, 2, SHAPE, dtype=np.uint8).view(np.bool_)
+    else:
+        a = _general_array(sorted(DECODE_CASES).index(name), fill)
+    mc = V.ModelChain(codecs, dt, fill, 3) if name in ("packbits_bool", "fixedscaleoffset") else \
+        O.OracleChain.from_metadata(codecs, dt, fill, 3)
+    enc = mc.encode(a)
+    exp = mc.decode(enc, SHAPE)
+    bad = bytearray(enc)
+    bad[pos] ^= mask
+    with pytest.raises((O.OracleError, V.PackBitsError)) as oe:  # the reference rejects the flipped stream too
+        mc.decode(bytes(bad), SHAPE)
+    return exp, enc, bytes(bad), getattr(oe.value, "status", None)
+
+
+def _levels(ctx):
+    s = ctx.pool_stats()
+    return s["dev_live"], s["host_live"]
+
+
+@pytest.fixture(scope="module")
+def decode_cases():
+    return {name: _decode_case(name) for name in DECODE_CASES}
+
+
+@pytest.mark.parametrize("out_device", [True, False], ids=["dev_out", "host_out"])
+@pytest.mark.parametrize("name", sorted(DECODE_CASES))
+def test_general_decode_returns_its_scratch(decode_cases, name, out_device):
+    import torch
+    from zarrs_amd import CodecChain, Context, ZgpuError, make_desc
+    from zarrs_amd import _lib as L
+    codecs, dt, fill, sels, _, _, want_status = DECODE_CASES[name]
+    exp, enc, bad, oracle_status = decode_cases[name]
+    if oracle_status is not None:
+        assert oracle_status == getattr(L, want_status)
+    ctx = Context(0)
+    ch = CodecChain.from_metadata(codecs, dt, fill, ctx)
+    good_d = torch.frombuffer(bytearray(enc), dtype=torch.uint8).cuda()  # torch memory, not the pools'
+    bad_d = torch.frombuffer(bytearray(bad), dtype=torch.uint8).cuda()
+    for start, sub in sels:
+        def output():
+            h = np.zeros(sub, exp.dtype)
+            return (torch.from_numpy(h.view(np.uint8)).cuda(), h.dtype) if out_device else (h, h.dtype)
+        out, odt = output()
+        before = _levels(ctx)
+        st = ch.decode_batch([make_desc(good_d, SHAPE, start, sub)], out, sub, enc_device=True)
+        assert _levels(ctx) == before, (name, start, "ok")
+        got = out.cpu().numpy().view(odt) if out_device else out
+        want = np.ascontiguousarray(exp[tuple(slice(s, s + n) for s, n in zip(start, sub))])
+        assert st == [0] and got.tobytes() == want.tobytes(), (name, start)
+        out, _ = output()
+        before = _levels(ctx)
+        with pytest.raises(ZgpuError) as ei:
+            ch.decode_batch([make_desc(bad_d, SHAPE, start, sub)], out, sub, enc_device=True)
+        assert _levels(ctx) == before, (name, start, "failed")
+        assert ei.value.status == getattr(L, want_status), (name, start)
+    del ch
+    ctx.close()
+
+
+ENC_SHAPE = [8, 16, 16]
+ENCODE_CASES = {
+    "fixed": (CODECS, "float32"),
+    "gzip": ([BYTES, GZIP], "float32"),
+    "shard_fixed": ([sh([4, 8, 8], [BYTES, CRC])], "float32"),
+    "shard_gzip": ([sh([4, 8, 8], [BYTES, GZIP])], "float32"),
+    "packbits": ([packbits(3, 12, "first_byte")], "uint16"),
+    "fixedscaleoffset": ([FSO, BYTES, ZSTD], "float32"),
+}
+
+
+def _encode_array(dt):
+    rng = np.random.default_rng(23)
+    if dt == "uint16":
+        return rng.integers(0, 1 << 16, ENC_SHAPE).astype(np.uint16)
+    a = np.round(1000 + rng.standard_normal(ENC_SHAPE) * 5).astype(np.float32)
+    a[0:4, 0:8, 0:8] = 0  # one all-fill inner chunk: omitted from a shard
+    return a
+
+
+@pytest.mark.parametrize("name", sorted(ENCODE_CASES))
+def test_encode_returns_its_scratch(name):
+    import torch
+    from zarrs_amd import CodecChain, Context
+    codecs, dt = ENCODE_CASES[name]
+    a = _encode_array(dt)
+    mc = V.ModelChain(codecs, dt, 0, 3)
+    ctx = Context(0)
+    ch = CodecChain.from_metadata(codecs, dt, 0, ctx)
+    d = _tensor(torch, a)
+    before = _levels(ctx)
+    parts = ch.encode_chunks(d, ENC_SHAPE, [[0, 0, 0]])
+    assert _levels(ctx) == before, name
+    got = bytes(parts[0].cpu().numpy())
+    # A compressor's or a shard's bytes need not equal the reference's (other matches, other layout of
+    # equal content), so every case is held to what the reference decodes the GPU's bytes to: its own
+    # decode of its own encoding, bit for bit; a fixed-size unsharded chain is also held bytewise.
+    assert mc.decode(got, ENC_SHAPE).tobytes() == mc.decode(mc.encode(a), ENC_SHAPE).tobytes(), name
+    if ch.encoded_size(ENC_SHAPE) >= 0 and "shard" not in name:
+        assert got == mc.encode(a), name  # a fixed-size chain: bytewise
+    del ch
+    ctx.close()
+
+
+def test_encode_pinned_returns_its_scratch():
+    from zarrs_amd import CodecChain, Context
+    from zarrs_amd import _lib as L
+    lib = L.load()
+    codecs = [sh([4, 8, 8], [BYTES, GZIP])]
+    a = _encode_array("float32")
+    oc = O.OracleChain.from_metadata(codecs, "float32", 0, 3)
+    ctx = Context(0)
+    ch = CodecChain.from_metadata(codecs, "float32", 0, ctx)
+    before = _levels(ctx)
+    p, n, r = C.c_void_p(), C.c_uint64(), C.c_void_p()
+    L.check(lib.zgpu_encode_pinned(ch._h, 3, L.u64s(ENC_SHAPE), a.ctypes.data, C.byref(p), C.byref(n), C.byref(r)))
+    try:
+        enc = bytes((C.c_uint8 * n.value).from_address(p.value))
+    finally:
+        lib.zgpu_result_release(r)
+    assert _levels(ctx) == before  # the result's pinned block went back with it
+    assert oc.decode(enc, ENC_SHAPE).tobytes() == a.tobytes()
+    del ch
+    ctx.close()

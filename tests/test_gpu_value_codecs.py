@@ -1,5 +1,5 @@
 """GPU decode and encode of the codecs that change element values or widths (packbits,
-numcodecs.fixedscaleoffset, bitround; kernels/value.hip and the composed paths of zgpu.cpp's
+numcodecs.fixedscaleoffset, bitround; kernels/value.hip and the composed paths of general.cpp's
 decode_general) against the numpy model composed with the CPU oracle (tests/value_codecs.py): bit-exact,
 no tolerance, encoded bytes in HBM and on the host, full and partial selections."""
 import ctypes as C

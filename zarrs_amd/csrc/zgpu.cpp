@@ -28,7 +28,9 @@
 #include "../../include/zgpu.h"
 #include "chain.hpp"
 #include "common.hpp"
+#include "ctx.hpp"
 #include "kernels/launch.hpp"
+#include "plan.hpp"
 #include "fsstore.hpp"
 #include "internal.hpp"
 #include "xfer.hpp"
@@ -36,240 +38,16 @@
 using namespace zgpu;
 
 namespace {
-
 thread_local std::string g_last_error;
-// device counters in the plan's control block (u64 each, cleared per execute)
-enum { CTR_ENC_BYTES = 0, CTR_ZSTD_SERIAL = 1, CTR_ZSTD_PARALLEL = 2, CTR_BLOSC_RERUN = 3, CTR_BLOSC_BLOCKS = 4,
-       CTR_ITEMS = 5, CTR_ZSTD_LATENCY = 6, CTR_BZ2_BLOCKS = 7, CTR_BZ2_ROUNDS = 8, CTR_N = 9 };  // CTR_ITEMS and CTR_BZ2_ROUNDS are host-side
-// internal ctl slots (not reported): a cached blosc layout was outgrown (the execution is re-run)
-enum { CTR_BLOSC_OVF = 31, CTR_SCRATCH = 30, CTR_ZSTD_NSER = 29, CTR_ZSTD_MAXBLK = 28 };  // not reported (device-side flags / sinks)
 thread_local uint64_t g_last_counters[CTR_N];
-// UnexpectedChunkDecodedSize detail of the last call's first DECODED_SIZE_MISMATCH descriptor
-struct SizeDetail {
-  int valid = 0;
-  uint64_t desc = 0, len = 0, expected = 0;
-};
 thread_local SizeDetail g_size_detail;
-
-struct HipFail {
-  hipError_t e;
-  const char *what;
-};
-#define HIPCHK(x)                                   \
-  do {                                              \
-    hipError_t _e = (x);                            \
-    if (_e != hipSuccess) throw HipFail{_e, #x};    \
-  } while (0)
-
 }  // namespace
 
-// ------------------------------------------------------------------------------------------------
-// Context: one per GPU. Owns a caching device allocator (grow-only pools reused across calls so a
-// steady-state decode performs no hipMalloc) and a small pool of "lanes" (a stream, two copy streams
-// and an ordering event): concurrent calls on one context each take a lane and run side by side on
-// the GPU (zarrs calls a codec from many rayon workers at once); a call that finds every lane busy
-// waits for one. ZGPU_CTX_LANES sets the pool size (default 8: coalesced drop-in calls measured
-// 10.7 -> 11.6 GiB/s going from 4 to 8, profiles/r04o_dropin_lanes_ab.txt).
-// ------------------------------------------------------------------------------------------------
-struct Coalescer;
-static void delete_coalescer(Coalescer *co);
-
-struct Lane {
-  hipStream_t stream = nullptr;              // the call's stream when the caller passes none
-  hipStream_t copy[2] = {nullptr, nullptr};  // H2D / D2H streams of the pipelined host paths (lazy)
-  hipStream_t out_hi = nullptr;               // high-priority stream of a coalesced batch's pack + D2H (lazy)
-  hipEvent_t order_ev = nullptr;              // legacy-stream -> lane-stream ordering (pick_stream)
-};
-
-// A lane's stream. HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default), and
-// kernels of different streams sharing a queue run one after the other: 8 lanes (plus their pack
-// streams) on 4 queues serialised the drop-in's concurrent calls. A stream with a CU mask gets a
-// hardware queue of its own; with every CU in the mask (ZGPU_LANE_QUEUES=1) it is an ordinary stream
-// otherwise. HIP creates CU-masked streams as blocking streams (ordered against the legacy null stream,
-// unlike the non-blocking lanes they replace), and has no flags argument for them: with
-// ZGPU_LANE_QUEUES=1, work a caller queues on the null stream serialises with the lanes.
-static hipError_t lane_stream_create(hipStream_t *s, int device) {
-  static const bool own = [] {
-    const char *e = std::getenv("ZGPU_LANE_QUEUES");
-    return e && std::atoi(e) != 0;
-  }();
-  if (own) {
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) {
-      std::vector<uint32_t> mask((ncu + 31) / 32, ~0u);
-      if (ncu % 32) mask.back() = (1u << (ncu % 32)) - 1;
-      const hipError_t e = hipExtStreamCreateWithCUMask(s, (uint32_t)mask.size(), mask.data());
-      if (e == hipSuccess) return e;
-      (void)hipGetLastError();
-    }
-  }
-  return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+int set_err(int st, const std::string &m) {
+  g_last_error = m;
+  return st;
 }
-
-struct zgpu_ctx {
-  int device = 0;
-  // Lifetime: zgpu_ctx_destroy drops the caller's reference; every chain, plan and cache created on
-  // the context holds one more, so a context outlives the objects that use it in whatever order a
-  // garbage-collected binding destroys them. The last reference frees the context (no HIP call runs
-  // from a static destructor: the library has none).
-  std::atomic<int64_t> refs{1};
-  std::mutex mu;  // the allocator pools
-  std::multimap<size_t, void *> free_dev;  // size -> ptr
-  std::map<void *, size_t> live_dev;
-  std::multimap<size_t, void *> free_host;
-  std::map<void *, size_t> live_host;
-  // lanes
-  std::mutex lane_mu;
-  std::condition_variable lane_cv;
-  std::vector<Lane *> lanes_all, lanes_free;
-  uint32_t max_lanes = 8;
-  hipStream_t peer = nullptr;  // peer copies of the multi-device read (lazy)
-  struct Coalescer *co = nullptr;  // ZGPU_COALESCE batching (lazy, under mu)
-
-  Lane *acquire_lane() {
-    std::unique_lock<std::mutex> lk(lane_mu);
-    while (lanes_free.empty()) {
-      if (lanes_all.size() < max_lanes) {
-        auto L = std::make_unique<Lane>();
-        HIPCHK(hipSetDevice(device));
-        HIPCHK(lane_stream_create(&L->stream, device));
-        lanes_all.push_back(L.get());
-        lanes_free.push_back(L.release());
-        break;
-      }
-      lane_cv.wait(lk);
-    }
-    Lane *L = lanes_free.back();
-    lanes_free.pop_back();
-    return L;
-  }
-  void release_lane(Lane *L) {
-    {
-      std::lock_guard<std::mutex> lk(lane_mu);
-      lanes_free.push_back(L);
-    }
-    lane_cv.notify_one();
-  }
-
-  // Device pool: sizes rounded up to classes (1/8 of a power of two above 1 MiB: <= 12.5 % slack) so
-  // that buffers of batches of varying size are reused instead of accumulating; the free blocks are
-  // capped (ZGPU_POOL_CAP_MB, default 16 GiB: the largest are returned to HIP beyond it). Without the
-  // cap, thousands of concurrent per-chunk calls (the codec plugin's pattern) of varying batch sizes
-  // grew the pool until the device had no memory left for a kernel's scratch.
-  size_t free_dev_bytes = 0;
-  size_t pool_cap = (size_t)16 << 30;
-  static size_t size_class(size_t b) {
-    b = std::max<size_t>(256, (b + 255) & ~(size_t)255);
-    if (b <= (1u << 20)) return b;
-    size_t p = (size_t)1 << (63 - __builtin_clzll(b - 1));  // largest power of two < b
-    const size_t step = p / 8;
-    return (b + step - 1) / step * step;
-  }
-  void trim_free_locked(size_t keep) {
-    while (free_dev_bytes > keep && !free_dev.empty()) {
-      auto it = std::prev(free_dev.end());  // the largest free block
-      (void)hipFree(it->second);
-      free_dev_bytes -= it->first;
-      free_dev.erase(it);
-    }
-  }
-  void *dev_alloc(size_t bytes) {
-    std::lock_guard<std::mutex> lk(mu);
-    bytes = size_class(bytes);
-    auto it = free_dev.lower_bound(bytes);
-    if (it != free_dev.end() && it->first <= bytes + bytes / 4 + (1u << 20)) {
-      void *p = it->second;
-      live_dev[p] = it->first;
-      free_dev_bytes -= it->first;
-      free_dev.erase(it);
-      return p;
-    }
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {  // release the cache and retry once
-      (void)hipGetLastError();
-      trim_free_locked(0);
-      HIPCHK(hipMalloc(&p, bytes));
-    }
-    live_dev[p] = bytes;
-    return p;
-  }
-  void dev_free(void *p) {
-    if (!p) return;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = live_dev.find(p);
-    if (it == live_dev.end()) return;
-    free_dev.emplace(it->second, p);
-    free_dev_bytes += it->second;
-    live_dev.erase(it);
-    if (free_dev_bytes > pool_cap) trim_free_locked(pool_cap / 2);
-  }
-  // Pinned host pool: the same size classes, free blocks capped at ZGPU_PINNED_CAP_MB (default 4 GiB;
-  // the largest go back to HIP beyond it) -- per-chunk pinned results of varying size otherwise
-  // accumulate a free block per distinct size
-  size_t free_host_bytes = 0;
-  size_t host_cap = (size_t)4 << 30;
-  void trim_host_locked(size_t keep) {
-    while (free_host_bytes > keep && !free_host.empty()) {
-      auto it = std::prev(free_host.end());
-      (void)hipHostFree(it->second);
-      free_host_bytes -= it->first;
-      free_host.erase(it);
-    }
-  }
-  void *host_alloc(size_t bytes) {
-    std::lock_guard<std::mutex> lk(mu);
-    bytes = std::max<size_t>(4096, size_class((bytes + 4095) & ~(size_t)4095));
-    auto it = free_host.lower_bound(bytes);
-    if (it != free_host.end() && it->first <= bytes + bytes / 4 + (1u << 20)) {
-      void *p = it->second;
-      live_host[p] = it->first;
-      free_host_bytes -= it->first;
-      free_host.erase(it);
-      return p;
-    }
-    void *p = nullptr;
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) {  // release the cache and retry once
-      (void)hipGetLastError();
-      trim_host_locked(0);
-      HIPCHK(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    }
-    live_host[p] = bytes;
-    return p;
-  }
-  void host_free(void *p) {
-    if (!p) return;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = live_host.find(p);
-    if (it == live_host.end()) return;
-    free_host.emplace(it->second, p);
-    free_host_bytes += it->second;
-    live_host.erase(it);
-    if (free_host_bytes > host_cap) trim_host_locked(host_cap / 2);
-  }
-  ~zgpu_ctx() {
-    (void)hipSetDevice(device);
-    for (Lane *L : lanes_all) {
-      if (L->stream) (void)hipStreamSynchronize(L->stream);
-      if (L->out_hi) (void)hipStreamSynchronize(L->out_hi);
-    }
-    for (auto &kv : free_dev) (void)hipFree(kv.second);
-    for (auto &kv : live_dev) (void)hipFree(kv.first);
-    for (auto &kv : free_host) (void)hipHostFree(kv.second);
-    for (auto &kv : live_host) (void)hipHostFree(kv.first);
-    for (Lane *L : lanes_all) {
-      if (L->stream) (void)hipStreamDestroy(L->stream);
-      if (L->order_ev) (void)hipEventDestroy(L->order_ev);
-      if (L->out_hi) (void)hipStreamDestroy(L->out_hi);
-      for (hipStream_t cs : L->copy)
-        if (cs) (void)hipStreamDestroy(cs);
-      delete L;
-    }
-    if (peer) (void)hipStreamDestroy(peer);
-    delete_coalescer(co);
-    (void)hipGetLastError();  // teardown failures must not surface in the caller's next HIP error check
-  }
-};
+SizeDetail &size_detail() { return g_size_detail; }
 
 void zgpu::ctx_ref(zgpu_ctx *c) {
   if (c) c->refs.fetch_add(1, std::memory_order_relaxed);
@@ -278,219 +56,9 @@ void zgpu::ctx_unref(zgpu_ctx *c) {
   if (c && c->refs.fetch_sub(1, std::memory_order_acq_rel) == 1) delete c;
 }
 
-// A call's lane for its whole duration (RAII).
-struct LaneScope {
-  zgpu_ctx *C;
-  Lane *L;
-  explicit LaneScope(zgpu_ctx *c) : C(c), L(c->acquire_lane()) {}
-  ~LaneScope() { C->release_lane(L); }
-  LaneScope(const LaneScope &) = delete;
-  LaneScope &operator=(const LaneScope &) = delete;
-};
-
-struct zgpu_chain {
-  zgpu_ctx *ctx;
-  std::shared_ptr<Chain> chain;
-  bool validate;
-};
-
-// ------------------------------------------------------------------------------------------------
-// Plan
-// ------------------------------------------------------------------------------------------------
-enum StageKind { ST_CRC32C, ST_GZIP, ST_ZSTD, ST_UNSHUFFLE, ST_BLOSC, ST_ADLER32, ST_FLETCHER32, ST_ZLIB, ST_BZ2 };
-// the checksum stages strip 4 bytes in place; every other stage materialises its output in a slot pool
-static bool strips_only(StageKind k) { return k == ST_CRC32C || k == ST_ADLER32 || k == ST_FLETCHER32; }
-static StageKind checksum_stage(CodecKind k) {
-  return k == CodecKind::Crc32c ? ST_CRC32C : k == CodecKind::Adler32 ? ST_ADLER32 : ST_FLETCHER32;
-}
-struct Stage {
-  StageKind kind;
-  int at_start = 0;
-  uint32_t elementsize = 0;
-  int pool = 0;  // destination slot pool for materialising stages
-};
-
-struct zgpu_plan {
-  zgpu_ctx *ctx = nullptr;
-  std::mutex mu;  // one execute / status at a time per plan
-  Lane own{};     // the plan's stream for executes without a caller stream (lazy)
-  std::shared_ptr<Chain> chain;
-  const Chain *leaf = nullptr;
-  bool validate = true;
-  uint32_t nd = 0;
-  uint64_t n_desc = 0;
-  uint32_t flags = 0;
-  std::vector<uint64_t> out_shape;
-  // host tables
-  std::vector<ZgItem> items;
-  std::vector<uint64_t> geom;
-  std::vector<uint32_t> item_desc_status;  // plan-time per-desc status
-  std::vector<ZgShard> shards;
-  std::vector<Stage> stages;
-  ZgScatter scatter{};
-  uint32_t scatter_mode = SCATTER_GENERIC;
-  uint64_t scatter_units = 0;
-  bool sharded = false, nested = false;
-  ZgIndexSpec ispec{}, ispec2{};  // ispec2: the middle shards' index (nested sharding)
-  std::vector<ZgItem> mids;       // nested: one record per intersecting middle shard
-  uint64_t slot_bytes = 0;
-  int n_pools = 0;
-  uint64_t alg_bytes_static = 0;  // decoded bytes written + (unsharded) encoded bytes + index bytes
-  // device buffers
-  ZgItem *d_items = nullptr, *d_items_init = nullptr;
-  uint64_t *d_geom = nullptr;
-  uint32_t *d_status = nullptr;
-  ZgShard *d_shards = nullptr;
-  uint64_t *d_index = nullptr;
-  uint32_t *d_shard_status = nullptr;
-  // nested sharding: middle shard records (resolved through the outer index each execution), their
-  // status, the middle shards as a shard table, and their decoded indexes
-  ZgItem *d_mids = nullptr, *d_mids_init = nullptr;
-  uint32_t *d_mid_status = nullptr, *d_shard_status2 = nullptr;
-  ZgShard *d_mid_shards = nullptr;
-  uint64_t *d_index2 = nullptr;
-  uint8_t *d_pool[2] = {nullptr, nullptr};
-  ZstdScratch zs{};  // block-parallel zstd scratch (allocated when the chain has zstd)
-  // side stream of the zstd sequence decoder (created on first use with the priority of the stream
-  // the plan first runs on; ZGPU_ZSTD_FORK=0 keeps one stream)
-  hipStream_t zside = nullptr;
-  hipEvent_t zev[2] = {nullptr, nullptr};
-  void zstd_fork(ZstdScratch &Z, hipStream_t s) {
-    static const bool on = [] {
-      const char *e = std::getenv("ZGPU_ZSTD_FORK");
-      return !e || std::atoi(e) != 0;
-    }();
-    if (!on || (flags & ZGPU_ONE_STREAM)) return;
-    if (!zside) {
-      int prio = 0;
-      if (s) (void)hipStreamGetPriority(s, &prio);
-      HIPCHK(hipStreamCreateWithPriority(&zside, hipStreamNonBlocking, prio));
-      for (hipEvent_t &e : zev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    Z.side = zside;
-    Z.ev_fork = zev[0];
-    Z.ev_join = zev[1];
-  }
-  // zstd in two pipelined halves (ZstdScratch::s2; blosc stream tables of many frames): opt-in with
-  // ZGPU_ZSTD_SPLIT=1 (blosc-zstd bench 32.6 -> 35.6 ms with it: the halves' kernels contend more than
-  // they overlap, profiles/r04an_zstd_split_ab.txt)
-  hipStream_t zs2 = nullptr;
-  hipEvent_t zev2[2] = {nullptr, nullptr};
-  void zstd_split(ZstdScratch &Z, hipStream_t s) {
-    const char *e = std::getenv("ZGPU_ZSTD_SPLIT");  // read per call (tests switch it)
-    if (!e || std::atoi(e) == 0 || !Z.side) return;
-    if (!zs2) {
-      int prio = 0;
-      if (s) (void)hipStreamGetPriority(s, &prio);
-      HIPCHK(hipStreamCreateWithPriority(&zs2, hipStreamNonBlocking, prio));
-      for (hipEvent_t &e : zev2) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    Z.s2 = zs2;
-    Z.ev_half = zev2[0];
-    Z.ev_done = zev2[1];
-  }
-  // blosc stage scratch (grown on demand; the stream table is sized from the frame headers)
-  struct Grow {
-    void *p = nullptr;
-    size_t n = 0;
-  };
-  Grow bl_info, bl_bases, bl_subs, bl_sub_status, bl_sub_kind, bl_blocks, bl_tmp, bl_zblks, bl_znblk, bl_zmode,
-      bl_zlit, bl_zseq, bl_zaux, bl_zser, bl_lzl, bl_zseg, bl_zrec, bl_zalias, bl_znorm, gz_crc, live_list,
-      ck_parts;  // ck_parts: the adler32 / fletcher32 stages' range sums
-  uint64_t in_len_hint = 0;  // the longest item before any stage, as far as the host knows: how many
-                             // workgroups a checksum stage gives an item (k_linsum_strip), not its result
-  uint8_t *bl_h = nullptr;  // pinned: BlInfo read-back (first execution)
-  size_t bl_h_n = 0;
-  void *grow(Grow &g, size_t bytes) {
-    if (g.n < bytes) {
-      ctx->dev_free(g.p);
-      g.p = ctx->dev_alloc(bytes);
-      g.n = bytes;
-    }
-    return g.p;
-  }
-  unsigned long long *d_counter = nullptr;
-  // control block: [counter (256 B) | per-item status (4 B each)], cleared by ONE memset and read
-  // back by ONE D2H copy into pinned memory (h_ctl) per execute
-  uint8_t *d_ctl = nullptr, *h_ctl = nullptr;
-  size_t ctl_bytes = 0;
-  // A tiled plan whose every item is a whole chunk of full, 16-B aligned tiles scatters with
-  // k_scatter_tiled_p (tiled_persistent_params; ZGPU_TILED_PERSIST=0: k_scatter_tiled): its constants
-  // and the output element offset of each item's origin
-  bool tiled_p = false;
-  ZgTiledP tiled_q{};
-  std::vector<uint64_t> origin;
-  uint64_t *d_origin = nullptr;
-  uint32_t last_path = SCATTER_GENERIC;  // zgpu_plan_scatter_path: of the last enqueue (before one: the plan's)
-  // host-input staging
-  uint8_t *d_enc_stage = nullptr;
-  uint64_t last_enc_bytes = 0;
-  uint64_t last_counters[CTR_N] = {};
-  uint8_t *last_out = nullptr;  // output of the last enqueue (a blosc layout overflow re-runs into it)
-  BlCaps bl_caps{};             // blosc stream-table capacities recorded by the first execution
-  bool bl_caps_valid = false, bl_caps_seen = false;
-  bool bl_direct = false;  // the blosc stage may write whole chunks straight into the output (BlDecode::dout)
-  bool gz_direct = false;  // the gzip stage may write whole chunks straight into the output (GzDirect)
-  GzDirect gz{};
-  // blosc as the last stage: per item the decoded byte range its selection needs ([0, max) for whole
-  // chunks); blocks outside it are not decoded (blosc_decompress_bytes_partial)
-  std::vector<uint64_t> bl_need;
-  uint64_t *d_bl_need = nullptr;
-  // zstd serial fallback: skipped once an execution of this plan had no serial item (a later one that
-  // has some is re-run by plan_statuses with the fallback launched)
-  bool zstd_serial_off = false, zstd_serial_skipped = false;
-  uint32_t *d_zser = nullptr;
-  uint32_t *d_order = nullptr;  // gzip stage: LPT dispatch order of the items
-  uint32_t *d_gz_seg = nullptr;  // gzip stage: symbol-record scratch of the segmented decode
-  uint64_t bz_rounds = 0;  // bz2 stage: rounds the last enqueue launched (ZGPU_CTR_BZ2_ROUNDS)
-  Bz2Scratch bz{};  // bz2 stage: block records, BWT vectors and pre-RLE1 bytes of one round of items
-  bool no_scatter = false;  // a whole-shard predecode plan: its bytes->bytes stages only (decode_general)
-
-  ~zgpu_plan() {
-    if (!ctx) return;
-    struct Unref {
-      zgpu_ctx *c;
-      ~Unref() { ctx_unref(c); }
-    } unref{ctx};  // after every buffer below went back to the context's pools
-    if (own.stream) {
-      (void)hipStreamSynchronize(own.stream);
-      (void)hipStreamDestroy(own.stream);
-    }
-    if (own.order_ev) (void)hipEventDestroy(own.order_ev);
-    void *bufs[] = {d_items, d_items_init, d_geom, d_shards, d_index, d_shard_status, d_mids, d_mids_init,
-                    d_mid_status, d_shard_status2, d_mid_shards, d_index2, d_bl_need,
-                    d_pool[0], d_pool[1], zs.blks, zs.nblk, zs.mode, zs.lit, zs.seq, d_ctl,
-                    d_enc_stage, d_zser, d_order, d_gz_seg, bz.base, zs.lit_rec, zs.ext, zs.ext_cnt, zs.norm, d_origin};
-    for (void *b : bufs) ctx->dev_free(b);
-    if (zside) {
-      (void)hipStreamSynchronize(zside);
-      (void)hipStreamDestroy(zside);
-    }
-    if (zs2) {
-      (void)hipStreamSynchronize(zs2);
-      (void)hipStreamDestroy(zs2);
-    }
-    for (hipEvent_t e : zev2)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : zev)
-      if (e) (void)hipEventDestroy(e);
-    for (Grow *g : {&bl_info, &bl_bases, &bl_subs, &bl_sub_status, &bl_sub_kind, &bl_blocks, &bl_tmp, &bl_zblks,
-                    &bl_znblk, &bl_zmode, &bl_zlit, &bl_zseq, &bl_zaux, &bl_zser, &bl_lzl, &bl_zseg, &bl_zrec, &bl_zalias,
-                    &bl_znorm, &gz_crc, &live_list, &ck_parts})
-      ctx->dev_free(g->p);
-    ctx->host_free(bl_h);
-    ctx->host_free(h_ctl);
-  }
-};
-
 static void reset_call_state() {
   for (uint64_t &c : g_last_counters) c = 0;
   g_size_detail = SizeDetail{};
-}
-
-static int set_err(int st, const std::string &m) {
-  g_last_error = m;
-  return st;
 }
 
 int zgpu::set_last_error(int status, const std::string &msg) { return set_err(status, msg); }
@@ -518,7 +86,7 @@ hipStream_t zgpu::ctx_copy_stream(zgpu_ctx *c) {  // nullptr on failure
 }
 
 // composed permutation of all array->array codecs: encoded axis a <-> decoded axis m[a]
-static void composed_axes(const Chain &c, uint32_t nd, uint32_t *m) {
+void composed_axes(const Chain &c, uint32_t nd, uint32_t *m) {
   for (uint32_t a = 0; a < nd; a++) m[a] = a;
   for (const Codec &k : c.a2a) {  // E_{k} axis a <-> E_{k-1} axis order[a]
     if (k.kind != CodecKind::Transpose) continue;  // the value codecs keep every element in its place
@@ -578,7 +146,7 @@ static void build_leaf_stages(zgpu_plan &P, const Chain &leaf, uint64_t nelem) {
 
 // ShardingIndex decode spec (sharding.rs:136-235, sharding_codec.rs:1262-1298): the index chain
 // must be bytes (+ crc32c), the only index_codecs zarrs' sharding writes and the GPU decodes.
-static ZgIndexSpec index_spec(const Codec &sharding, uint64_t n_inner, bool validate) {
+ZgIndexSpec index_spec(const Codec &sharding, uint64_t n_inner, bool validate) {
   const Chain &xc = *sharding.index;
   if (xc.a2b.kind != CodecKind::Bytes || !xc.a2a.empty())
     throw ChainError{ZGPU_UNSUPPORTED, "index_codecs must be bytes (+crc32c)"};
@@ -950,24 +518,23 @@ static void plan_build(zgpu_plan &P, const zgpu_chunk_desc *descs) {
   }
 }
 
-static void plan_upload(zgpu_plan &P, hipStream_t us) {
-  zgpu_ctx &C = *P.ctx;
+void plan_upload(zgpu_plan &P, hipStream_t us) {
   const size_t ni = P.items.size();
   if (ni) {
-    P.d_items = (ZgItem *)C.dev_alloc(ni * sizeof(ZgItem));
-    P.d_items_init = (ZgItem *)C.dev_alloc(ni * sizeof(ZgItem));
-    P.d_geom = (uint64_t *)C.dev_alloc(P.geom.size() * 8);
+    P.d_items = P.mem.dev<ZgItem>(ni);
+    P.d_items_init = P.mem.dev<ZgItem>(ni);
+    P.d_geom = P.mem.dev<uint64_t>(P.geom.size());
     HIPCHK(hipMemcpyAsync(P.d_items_init, P.items.data(), ni * sizeof(ZgItem), hipMemcpyHostToDevice, us));
     HIPCHK(hipMemcpyAsync(P.d_geom, P.geom.data(), P.geom.size() * 8, hipMemcpyHostToDevice, us));
-    for (int k = 0; k < P.n_pools; k++) P.d_pool[k] = (uint8_t *)C.dev_alloc(ni * P.slot_bytes);
+    for (int k = 0; k < P.n_pools; k++) P.d_pool[k] = P.mem.dev<uint8_t>(ni * P.slot_bytes);
     if (!P.bl_need.empty()) {
-      P.d_bl_need = (uint64_t *)C.dev_alloc(P.bl_need.size() * 8);
+      P.d_bl_need = P.mem.dev<uint64_t>(P.bl_need.size());
       HIPCHK(hipMemcpyAsync(P.d_bl_need, P.bl_need.data(), P.bl_need.size() * 8, hipMemcpyHostToDevice, us));
     }
     for (const Stage &s : P.stages) {
       if ((s.kind == ST_GZIP || s.kind == ST_ZLIB) && !P.d_order) {
-        P.d_order = (uint32_t *)C.dev_alloc(ni * 4);
-        if (const uint64_t b = gzip_seg_scratch_bytes((uint32_t)ni)) P.d_gz_seg = (uint32_t *)C.dev_alloc(b);
+        P.d_order = P.mem.dev<uint32_t>(ni);
+        if (const uint64_t b = gzip_seg_scratch_bytes((uint32_t)ni)) P.d_gz_seg = (uint32_t *)P.mem.dev<uint8_t>(b);
       }
       if (s.kind == ST_BZ2 && !P.bz.base) {
         // 5 x slot_bytes of BWT vector (+ 1.25 x of bytes before RLE1, + block records) per item: a batch
@@ -980,28 +547,28 @@ static void plan_upload(zgpu_plan &P, hipStream_t us) {
         per_round = std::min<uint64_t>(per_round, std::max<uint64_t>(1, (1u << 30) / P.bz.cap));
         P.bz.round_items = (uint32_t)std::min<uint64_t>(per_round, ni);
         const uint64_t items_bytes = P.bz.round_items * P.bz.item_bytes;  // a multiple of 256
-        P.bz.base = (uint8_t *)C.dev_alloc(items_bytes + bz2_list_bytes(P.bz.round_items, P.bz.cap));
+        P.bz.base = P.mem.dev<uint8_t>(items_bytes + bz2_list_bytes(P.bz.round_items, P.bz.cap));
         P.bz.lists = (uint32_t *)(P.bz.base + items_bytes);
       }
       if (s.kind == ST_ZSTD && !P.zs.blks) {
         uint64_t blk_bytes;
         zstd_scratch_layout(P.slot_bytes, P.zs.blk_cap, blk_bytes, P.zs.lit_stride, P.zs.seq_cap);
-        P.zs.blks = C.dev_alloc(ni * (uint64_t)P.zs.blk_cap * blk_bytes);
-        P.zs.norm = (int16_t *)C.dev_alloc(ni * (uint64_t)P.zs.blk_cap * zstd_norm_bytes());
-        P.zs.nblk = (uint32_t *)C.dev_alloc(ni * 4);
-        P.zs.mode = (uint32_t *)C.dev_alloc(ni * 4);
-        P.zs.lit = (uint8_t *)C.dev_alloc(ni * P.zs.lit_stride);
-        P.zs.seq = (uint32_t *)C.dev_alloc(ni * P.zs.seq_cap * 12);
-        P.d_zser = (uint32_t *)C.dev_alloc(ni * 4);
+        P.zs.blks = P.mem.dev<uint8_t>(ni * (uint64_t)P.zs.blk_cap * blk_bytes);
+        P.zs.norm = (int16_t *)P.mem.dev<uint8_t>(ni * (uint64_t)P.zs.blk_cap * zstd_norm_bytes());
+        P.zs.nblk = P.mem.dev<uint32_t>(ni);
+        P.zs.mode = P.mem.dev<uint32_t>(ni);
+        P.zs.lit = P.mem.dev<uint8_t>(ni * P.zs.lit_stride);
+        P.zs.seq = P.mem.dev<uint32_t>(ni * P.zs.seq_cap * 3);
+        P.d_zser = P.mem.dev<uint32_t>(ni);
         P.zs.ser_list = P.d_zser;
-        if (const uint64_t rb = zstd_lit_rec_bytes(P.zs.lit_rec_wgs)) P.zs.lit_rec = (uint8_t *)C.dev_alloc(rb);
+        if (const uint64_t rb = zstd_lit_rec_bytes(P.zs.lit_rec_wgs)) P.zs.lit_rec = P.mem.dev<uint8_t>(rb);
         static const uint64_t par_max = [] {  // ZGPU_ZSTD_XPAR_MB: the latency mode's batch limit (tuning)
           const char *e = std::getenv("ZGPU_ZSTD_XPAR_MB");
           return e ? (uint64_t)std::strtoull(e, nullptr, 10) << 20 : ZPAR_MAX_BYTES;
         }();
         if (ni * P.slot_bytes <= par_max) {  // the window executor's latency mode (few frames)
-          P.zs.ext = (uint32_t *)C.dev_alloc(2 * ni * P.slot_bytes * 4);
-          P.zs.ext_cnt = (unsigned long long *)C.dev_alloc(ZEXT_ROUNDS * 8);
+          P.zs.ext = P.mem.dev<uint32_t>(2 * ni * P.slot_bytes);
+          P.zs.ext_cnt = P.mem.dev<unsigned long long>(ZEXT_ROUNDS);
           P.zs.ext_items = ni;
         }
       }
@@ -1024,10 +591,10 @@ static void plan_upload(zgpu_plan &P, hipStream_t us) {
     if (ni && (s.kind == ST_ADLER32 || s.kind == ST_FLETCHER32))
       P.grow(P.ck_parts, linsum_scratch_bytes((uint32_t)ni, std::max(P.in_len_hint, P.slot_bytes)));
   P.ctl_bytes = 256 + ni * 4;
-  P.d_ctl = (uint8_t *)C.dev_alloc(P.ctl_bytes);
-  P.h_ctl = (uint8_t *)C.host_alloc(P.ctl_bytes);
+  P.d_ctl = P.mem.dev<uint8_t>(P.ctl_bytes);
+  P.h_ctl = P.mem.pinned<uint8_t>(P.ctl_bytes);
   if (P.tiled_p) {
-    P.d_origin = (uint64_t *)C.dev_alloc(ni * 8);
+    P.d_origin = P.mem.dev<uint64_t>(ni);
     HIPCHK(hipMemcpyAsync(P.d_origin, P.origin.data(), ni * 8, hipMemcpyHostToDevice, us));
   }
   P.d_counter = (unsigned long long *)P.d_ctl;
@@ -1038,20 +605,20 @@ static void plan_upload(zgpu_plan &P, hipStream_t us) {
   P.zs.max_nblk = P.d_counter + CTR_ZSTD_MAXBLK;
   if (const char *e = std::getenv("ZGPU_ZSTD_FORCE_SERIAL")) P.zs.force_serial = std::atoi(e) != 0;
   if (!P.shards.empty()) {
-    P.d_shards = (ZgShard *)C.dev_alloc(P.shards.size() * sizeof(ZgShard));
-    P.d_index = (uint64_t *)C.dev_alloc(P.shards.size() * P.ispec.n_inner * 16);
-    P.d_shard_status = (uint32_t *)C.dev_alloc(P.shards.size() * 4);
+    P.d_shards = P.mem.dev<ZgShard>(P.shards.size());
+    P.d_index = P.mem.dev<uint64_t>(P.shards.size() * P.ispec.n_inner * 2);
+    P.d_shard_status = P.mem.dev<uint32_t>(P.shards.size());
     HIPCHK(hipMemcpyAsync(P.d_shards, P.shards.data(), P.shards.size() * sizeof(ZgShard), hipMemcpyHostToDevice,
                           us));
   }
   if (!P.mids.empty()) {
     const size_t nm = P.mids.size();
-    P.d_mids = (ZgItem *)C.dev_alloc(nm * sizeof(ZgItem));
-    P.d_mids_init = (ZgItem *)C.dev_alloc(nm * sizeof(ZgItem));
-    P.d_mid_status = (uint32_t *)C.dev_alloc(nm * 4);
-    P.d_shard_status2 = (uint32_t *)C.dev_alloc(nm * 4);
-    P.d_mid_shards = (ZgShard *)C.dev_alloc(nm * sizeof(ZgShard));
-    P.d_index2 = (uint64_t *)C.dev_alloc(nm * P.ispec2.n_inner * 16);
+    P.d_mids = P.mem.dev<ZgItem>(nm);
+    P.d_mids_init = P.mem.dev<ZgItem>(nm);
+    P.d_mid_status = P.mem.dev<uint32_t>(nm);
+    P.d_shard_status2 = P.mem.dev<uint32_t>(nm);
+    P.d_mid_shards = P.mem.dev<ZgShard>(nm);
+    P.d_index2 = P.mem.dev<uint64_t>(nm * P.ispec2.n_inner * 2);
     HIPCHK(hipMemcpyAsync(P.d_mids_init, P.mids.data(), nm * sizeof(ZgItem), hipMemcpyHostToDevice, us));
   }
 }
@@ -1062,7 +629,6 @@ static void plan_upload(zgpu_plan &P, hipStream_t us) {
 // the sizes as capacities; later executions lay the table out on the device against them
 // (k_blosc_layout) and stay asynchronous. A later input that outgrows them is re-run by plan_statuses.
 static void blosc_stage(zgpu_plan &P, const Stage &st, uint8_t *out, hipStream_t s) {
-  zgpu_ctx &C = *P.ctx;
   const uint32_t ni = (uint32_t)P.items.size();
   uint8_t *dst = P.d_pool[st.pool];
   BlInfo *info = (BlInfo *)P.grow(P.bl_info, ni * sizeof(BlInfo));
@@ -1081,12 +647,7 @@ static void blosc_stage(zgpu_plan &P, const Stage &st, uint8_t *out, hipStream_t
   BlCaps &caps = P.bl_caps;
   const bool cached = P.bl_caps_valid;
   if (!cached) {
-    const size_t hbytes = ni * sizeof(BlInfo);
-    if (P.bl_h_n < hbytes) {
-      C.host_free(P.bl_h);
-      P.bl_h = (uint8_t *)C.host_alloc(hbytes);
-      P.bl_h_n = hbytes;
-    }
+    if (!P.bl_h) P.bl_h = (uint8_t *)P.mem.pinned<BlInfo>(ni);  // (a plan's item count is fixed)
     HIPCHK(hipMemcpyAsync(P.bl_h, info, ni * sizeof(BlInfo), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     std::vector<BlInfo> hi(ni);
@@ -1163,7 +724,7 @@ static void blosc_stage(zgpu_plan &P, const Stage &st, uint8_t *out, hipStream_t
 }
 
 // Enqueue the decode of an uploaded plan on stream s.
-static void plan_enqueue(zgpu_plan &P, uint8_t *out, hipStream_t s) {
+void plan_enqueue(zgpu_plan &P, uint8_t *out, hipStream_t s) {
   const uint32_t ni = (uint32_t)P.items.size();
   P.last_out = out;
   P.bz_rounds = 0;
@@ -1324,7 +885,7 @@ static void size_detail(zgpu_plan &P, uint64_t d, const uint32_t *st, hipStream_
 
 // Read back per-item statuses and reduce them to per-descriptor statuses. Returns the first
 // non-zero descriptor status.
-static int plan_statuses(zgpu_plan &P, int32_t *status, hipStream_t s) {
+int plan_statuses(zgpu_plan &P, int32_t *status, hipStream_t s) {
   const size_t ni = P.items.size();
   HIPCHK(hipMemcpyAsync(P.h_ctl, P.d_ctl, P.ctl_bytes, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -1371,11 +932,9 @@ static int plan_statuses(zgpu_plan &P, int32_t *status, hipStream_t s) {
   return first;
 }
 
-static zgpu_plan *plan_new(zgpu_ctx *ctx, const std::shared_ptr<Chain> &chain, bool validate, uint32_t nd,
+zgpu_plan *plan_new(zgpu_ctx *ctx, const std::shared_ptr<Chain> &chain, bool validate, uint32_t nd,
                            const zgpu_chunk_desc *descs, uint64_t n, const uint64_t *out_shape, uint32_t flags) {
-  auto P = std::make_unique<zgpu_plan>();
-  ctx_ref(ctx);
-  P->ctx = ctx;
+  auto P = std::make_unique<zgpu_plan>(ctx);
   P->chain = chain;
   P->validate = validate && !(flags & ZGPU_NO_VALIDATE);
   P->nd = nd;
@@ -1394,7 +953,7 @@ static zgpu_plan *plan_new(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *d
 // hip_stream NULL: the context's stream, ordered after all work already queued on the legacy
 // default stream (where torch's default stream and plain hipMemcpy/kernels land), so device buffers a
 // caller produced there are complete before the decode reads or writes them.
-static hipStream_t pick_stream(Lane *L, void *s) {
+hipStream_t pick_stream(Lane *L, void *s) {
   if (s) return (hipStream_t)s;
   if (!L->order_ev) HIPCHK(hipEventCreateWithFlags(&L->order_ev, hipEventDisableTiming));
   HIPCHK(hipEventRecord(L->order_ev, nullptr));
@@ -1410,859 +969,8 @@ static Lane *plan_lane(zgpu_plan &P) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// General decode: the chains and batches one fused plan does not take, composed from fused plans
-// (CodecChain composes any chain, codec_chain.rs:192-229, and zarrs decodes every chunk through its
-// own chain and shape):
-//  * descriptors of more than one chunk (shard) shape: one plan per shape, on one stream;
-//  * bytes->bytes codecs after sharding_indexed (a checksum or compressor over the whole shard): the
-//    shards go through those codecs first, stage by stage (the leaf-chunk kernels; slots sized from
-//    the streams' own size fields), then decode as plain shards;
-//  * sharding nested more than two deep, or codecs around a nested sharding_indexed: the outer shard
-//    indexes are decoded on the device and read back, and the intersecting middle shards become the
-//    descriptors of the inner chain (recursively, sharding.rs:107-126).
-// Synchronous (per-stage read-backs); per-descriptor statuses, first failing item of a descriptor.
-// ------------------------------------------------------------------------------------------------
-static bool fused_plannable(const Chain &top) {
-  if (chain_has_value_codec(top) || top.a2b.kind == CodecKind::PackBits) return false;
-  if (top.a2b.kind != CodecKind::Sharding) return true;
-  if (!top.b2b.empty()) return false;
-  const Chain &mid = *top.a2b.inner;
-  if (mid.a2b.kind != CodecKind::Sharding) return true;
-  return mid.a2a.empty() && mid.b2b.empty() && mid.a2b.inner->a2b.kind != CodecKind::Sharding;
-}
-
-static bool same_shape(const zgpu_chunk_desc &a, const zgpu_chunk_desc &b, uint32_t nd) {
-  for (uint32_t d = 0; d < nd; d++)
-    if (a.chunk_shape[d] != b.chunk_shape[d]) return false;
-  return true;
-}
-
-static bool uniform_shapes(const zgpu_chunk_desc *descs, uint64_t n, uint32_t nd) {
-  for (uint64_t i = 1; i < n; i++)
-    if (!same_shape(descs[0], descs[i], nd)) return false;
-  return true;
-}
-
-static bool desc_geometry_ok(const zgpu_chunk_desc &D, uint32_t nd, const uint64_t *out_shape) {
-  for (uint32_t d = 0; d < nd; d++)
-    if (D.sel_start[d] + D.sel_shape[d] > D.chunk_shape[d] || D.out_start[d] + D.sel_shape[d] > out_shape[d])
-      return false;
-  return true;
-}
-
-static uint64_t sel_volume(const zgpu_chunk_desc &D, uint32_t nd) {
-  uint64_t v = 1;
-  for (uint32_t d = 0; d < nd; d++) v *= D.sel_shape[d];
-  return v;
-}
-
-static bool sel_full(const zgpu_chunk_desc &D, uint32_t nd) {
-  for (uint32_t d = 0; d < nd; d++)
-    if (D.sel_start[d] != 0 || D.sel_shape[d] != D.chunk_shape[d]) return false;
-  return true;
-}
-
-// The box [org, org + shape) of a device array (C order, array_shape) into dst + dst_off, compact
-// (k_box_copy: one wave per contiguous run).
-static void pack_box(const uint8_t *src, uint32_t nd, const uint64_t *array_shape, const uint64_t *org,
-                     const uint64_t *shape, uint32_t es, uint8_t *dst, uint64_t dst_off, hipStream_t s) {
-  const BoxRuns R = box_runs(nd, array_shape, org, shape, es);
-  ZgBoxCopy P{};
-  P.outer = R.outer;
-  uint64_t cs = R.run_bytes;  // compact strides of the outer axes
-  for (int d = (int)R.outer - 1; d >= 0; d--) {
-    P.shape[d] = R.shape[d];
-    P.src_stride[d] = R.stride[d];
-    P.dst_stride[d] = cs;
-    cs *= R.shape[d];
-  }
-  P.src_base = R.base;
-  P.dst_base = dst_off;
-  P.run_bytes = R.run_bytes;
-  P.n_runs = R.n_runs;
-  HIPCHK(launch_box_copy(src, dst, P, s));
-}
-
-struct GeneralCall {
-  zgpu_ctx *C;
-  bool validate;
-  uint32_t nd;
-  uint8_t *out;  // device output array
-  const uint64_t *out_shape;
-  uint32_t flags;
-  hipStream_t s;
-  std::vector<std::unique_ptr<zgpu_plan>> keep;  // whole-shard decode slots, alive until the call ends
-};
-
-static void decode_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
-                           uint64_t n, int32_t *status);
-
-// Decode `sub` (sub-descriptor k belongs to caller descriptor owner[k]) and merge: a caller
-// descriptor keeps its first error.
-static void run_sub(GeneralCall &G, const std::shared_ptr<Chain> &chain, const std::vector<zgpu_chunk_desc> &sub,
-                    const std::vector<uint64_t> &owner, int32_t *status) {
-  if (sub.empty()) return;
-  std::vector<int32_t> st(sub.size(), 0);
-  const bool had_detail = g_size_detail.valid;
-  decode_general(G, chain, sub.data(), sub.size(), st.data());
-  if (!had_detail && g_size_detail.valid) g_size_detail.desc = owner[g_size_detail.desc];
-  for (size_t k = 0; k < sub.size(); k++)
-    if (st[k] && !status[owner[k]]) status[owner[k]] = st[k];
-}
-
-// One bytes->bytes codec applied to whole shards (items[i] = shard i's current bytes; ist[i] its
-// status): decoded by a stages-only plan whose slots hold the decoded shards. Compressors size the
-// slots from the streams (kernels/probe.hip); a gzip member longer than its ISIZE hint is re-run
-// with larger slots up to DEFLATE's 1032:1 bound, and so is a zlib stream, which carries no size:
-// its slots start at four times the encoded shard. A bz2 stream carries no size either and has no
-// useful ratio bound (50 bytes decode to 45,899,000 zeros), so only the slot limit ends its regrowing.
-static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &items, std::vector<int32_t> &ist) {
-  std::vector<uint32_t> todo;
-  for (uint32_t i = 0; i < items.size(); i++)
-    if (!ist[i]) todo.push_back(i);
-  if (todo.empty()) return;
-  Stage st{};
-  uint32_t hint_kind = UINT32_MAX;
-  switch (k.kind) {
-    case CodecKind::Crc32c:
-    case CodecKind::Adler32:
-    case CodecKind::Fletcher32: st.kind = checksum_stage(k.kind); st.at_start = k.at_start; break;
-    case CodecKind::Gzip: st.kind = ST_GZIP; hint_kind = SIZE_HINT_GZIP; break;
-    case CodecKind::Zlib: st.kind = ST_ZLIB; break;  // no size in the stream: the regrow loop below finds it
-    case CodecKind::Bz2: st.kind = ST_BZ2; break;    // likewise
-    case CodecKind::Zstd: st.kind = ST_ZSTD; hint_kind = SIZE_HINT_ZSTD; break;
-    case CodecKind::Blosc: st.kind = ST_BLOSC; hint_kind = SIZE_HINT_BLOSC; break;
-    case CodecKind::Shuffle: st.kind = ST_UNSHUFFLE; st.elementsize = k.elementsize; break;
-    default: throw ChainError{ZGPU_UNSUPPORTED, "codec '" + k.name + "' after sharding_indexed"};
-  }
-  uint64_t cap = 0;
-  if (st.kind == ST_UNSHUFFLE) {
-    for (uint32_t t : todo) cap = std::max(cap, items[t].len);
-  } else if (st.kind == ST_ZLIB || st.kind == ST_BZ2) {
-    for (uint32_t t : todo) cap = std::max(cap, items[t].len * 4);  // a first guess; regrown 8x on a mismatch
-  } else if (hint_kind != UINT32_MAX) {
-    const uint32_t nt = (uint32_t)todo.size();
-    std::vector<ZgItem> hi(nt);
-    for (uint32_t j = 0; j < nt; j++) hi[j] = items[todo[j]];
-    ZgItem *d_it = (ZgItem *)G.C->dev_alloc(nt * sizeof(ZgItem));
-    uint8_t *d_buf = (uint8_t *)G.C->dev_alloc(nt * 12);
-    std::vector<uint64_t> h(nt, 0);
-    hipError_t e = hipMemcpyAsync(d_it, hi.data(), nt * sizeof(ZgItem), hipMemcpyHostToDevice, G.s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_buf + nt * 8, 0, nt * 4, G.s);
-    if (e == hipSuccess)
-      e = launch_size_hint(d_it, (const uint32_t *)(d_buf + nt * 8), nt, hint_kind, (uint64_t *)d_buf, G.s);
-    if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d_buf, nt * 8, hipMemcpyDeviceToHost, G.s);
-    if (e == hipSuccess) e = hipStreamSynchronize(G.s);
-    G.C->dev_free(d_it);
-    G.C->dev_free(d_buf);
-    if (e != hipSuccess) throw HipFail{e, "whole-shard size hints"};
-    for (uint64_t v : h) cap = std::max(cap, v);
-  }
-  cap = std::max<uint64_t>(cap, 256);
-  // one stages-only plan over `set` with slots of `c` bytes; statuses in s, decoded items in res
-  auto run = [&](const std::vector<uint32_t> &set, uint64_t c, std::vector<int32_t> &s, std::vector<ZgItem> &res) {
-    auto P = std::make_unique<zgpu_plan>();
-    ctx_ref(G.C);  // ~zgpu_plan drops it
-    P->ctx = G.C;
-    P->validate = G.validate;
-    P->nd = 1;
-    P->n_desc = set.size();
-    P->flags = G.flags;
-    P->out_shape = {1};
-    P->item_desc_status.assign(set.size(), 0);
-    for (size_t j = 0; j < set.size(); j++) {
-      ZgItem it = items[set[j]];
-      it.desc = (uint32_t)j;
-      P->items.push_back(it);
-    }
-    st.pool = 0;
-    P->stages = {st};
-    P->n_pools = strips_only(st.kind) ? 0 : 1;
-    P->slot_bytes = (c + 255) & ~(uint64_t)255;
-    P->no_scatter = true;
-    plan_upload(*P, G.s);
-    plan_enqueue(*P, nullptr, G.s);
-    s.assign(set.size(), 0);
-    const SizeDetail keep_detail = g_size_detail;
-    plan_statuses(*P, s.data(), G.s);
-    g_size_detail = keep_detail;  // a shard has no expected decoded size
-    res.resize(set.size());
-    HIPCHK(hipMemcpyAsync(res.data(), P->d_items, set.size() * sizeof(ZgItem), hipMemcpyDeviceToHost, G.s));
-    HIPCHK(hipStreamSynchronize(G.s));
-    if (std::find(s.begin(), s.end(), 0) != s.end()) G.keep.push_back(std::move(P));  // slots in use
-  };
-  // gzip's ISIZE is the decoded size modulo 2^32 (RFC 1952), only a hint: a member that outgrows its
-  // slot is re-run ALONE with 8x larger slots, up to DEFLATE's 1032:1 bound and the slot limit
-  // (ZGPU_SHARD_SLOT_LIMIT, default 64 GiB); past the limit it fails by itself with
-  // DECODED_SIZE_MISMATCH instead of sizing every retried shard's slot for the largest
-  static const uint64_t slot_limit = [] {
-    const char *e = std::getenv("ZGPU_SHARD_SLOT_LIMIT");
-    const uint64_t v = e ? std::strtoull(e, nullptr, 10) : 0;
-    return v ? v : (64ull << 30);
-  }();
-  std::vector<int32_t> s;
-  std::vector<ZgItem> res;
-  run(todo, std::min(cap, slot_limit), s, res);
-  auto settle = [&](uint32_t t, int32_t sj, const ZgItem &r) {
-    ist[t] = sj;
-    if (!sj) {
-      items[t].src = r.src;
-      items[t].len = r.len;
-    }
-  };
-  std::vector<uint32_t> again;
-  auto bound_of = [&](uint32_t t) {
-    return st.kind == ST_BZ2 ? slot_limit : std::min(items[t].len * 1032 + 1024, slot_limit);
-  };
-  for (size_t j = 0; j < todo.size(); j++) {
-    const uint32_t t = todo[j];
-    const uint64_t bound = bound_of(t);
-    if (s[j] == ZGPU_DECODED_SIZE_MISMATCH && (st.kind == ST_GZIP || st.kind == ST_ZLIB || st.kind == ST_BZ2) &&
-        cap < bound)
-      again.push_back(t);
-    else
-      settle(t, s[j], res[j]);
-  }
-  for (uint32_t t : again) {
-    const uint64_t bound = bound_of(t);
-    for (uint64_t c = std::min(cap * 8, bound);; c = std::min(c * 8, bound)) {
-      run({t}, c, s, res);
-      if (!(s[0] == ZGPU_DECODED_SIZE_MISMATCH && c < bound)) {
-        settle(t, s[0], res[0]);
-        break;
-      }
-    }
-  }
-}
-
-// bytes->bytes codecs after sharding_indexed: decode every selected shard through them (reverse
-// order, codec_chain.rs:612-617), then read the decoded shards through the chain without them.
-static void predecode_shards(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
-                             uint64_t n, int32_t *status) {
-  const Chain &top = *chain;
-  const uint32_t nd = G.nd;
-  std::vector<ZgItem> items;
-  std::vector<uint64_t> owner;
-  for (uint64_t i = 0; i < n; i++) {
-    const zgpu_chunk_desc &D = descs[i];
-    if (!desc_geometry_ok(D, nd, G.out_shape)) {
-      status[i] = ZGPU_INVALID_ARGUMENT;
-      continue;
-    }
-    if (!D.enc || sel_volume(D, nd) == 0) continue;
-    ZgItem it{};
-    it.src = (uint64_t)D.enc;
-    it.len = D.enc_len;
-    it.desc = (uint32_t)items.size();
-    it.flags = sel_full(D, nd) ? 0u : ZG_ITEM_PARTIAL;  // a partial read strips crc32c unverified
-    items.push_back(it);
-    owner.push_back(i);
-  }
-  std::vector<int32_t> ist(items.size(), 0);
-  for (int k = (int)top.b2b.size() - 1; k >= 0; k--) shard_stage(G, top.b2b[k], items, ist);
-  auto bare = std::make_shared<Chain>(top);
-  bare->b2b.clear();
-  std::vector<zgpu_chunk_desc> sub;
-  std::vector<uint64_t> sub_owner;
-  size_t j = 0;
-  for (uint64_t i = 0; i < n; i++) {
-    if (status[i]) continue;
-    zgpu_chunk_desc D = descs[i];
-    if (j < owner.size() && owner[j] == i) {
-      const size_t t = j++;
-      if (ist[t]) {
-        status[i] = ist[t];
-        continue;
-      }
-      D.enc = (const void *)items[t].src;
-      D.enc_len = items[t].len;
-    }
-    sub.push_back(D);
-    sub_owner.push_back(i);
-  }
-  run_sub(G, bare, sub, sub_owner, status);
-}
-
-// A sharded chain whose subchunks are shards the fused plan cannot take (codecs around them, or
-// sharding below them again): the outer indexes decode on the device (k_shard_index, checksums
-// verified) and come back to the host, and every intersecting middle shard becomes a descriptor of
-// the inner chain (sharding_codec.rs:617-707 per subchunk; an empty one decodes to the fill value).
-static void nested_host(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
-                        uint64_t n, int32_t *status) {
-  const Chain &top = *chain;
-  const uint32_t nd = G.nd;
-  const std::vector<uint64_t> &ms = top.a2b.inner_shape;
-  if (ms.size() != nd) throw ChainError{ZGPU_INVALID_ARGUMENT, "sharding chunk_shape rank"};
-  uint64_t cps[ZG_MAXD], n_inner = 0;
-  std::vector<ZgShard> shards;
-  std::vector<uint64_t> shard_of(n, UINT64_MAX);
-  for (uint64_t i = 0; i < n; i++) {
-    const zgpu_chunk_desc &D = descs[i];
-    bool ok = desc_geometry_ok(D, nd, G.out_shape);
-    uint64_t ni = 1;
-    for (uint32_t d = 0; d < nd && ok; d++) {
-      if (!ms[d] || D.chunk_shape[d] % ms[d]) ok = false;  // calculate_chunks_per_shard (sharding.rs:136-154)
-      else {
-        cps[d] = D.chunk_shape[d] / ms[d];
-        ni *= cps[d];
-      }
-    }
-    if (!ok) {
-      status[i] = ZGPU_INVALID_ARGUMENT;
-      continue;
-    }
-    n_inner = ni;  // one shard shape per call (decode_general groups by shape)
-    if (D.enc && sel_volume(D, nd)) {
-      shard_of[i] = shards.size();
-      shards.push_back(ZgShard{(uint64_t)D.enc, D.enc_len});
-    }
-  }
-  std::vector<uint64_t> index;
-  std::vector<uint32_t> sst;
-  if (!shards.empty()) {
-    const ZgIndexSpec spec = index_spec(top.a2b, n_inner, G.validate);
-    const size_t ns = shards.size();
-    index.resize(ns * n_inner * 2);
-    sst.resize(ns);
-    ZgShard *d_sh = (ZgShard *)G.C->dev_alloc(ns * sizeof(ZgShard));
-    uint64_t *d_idx = (uint64_t *)G.C->dev_alloc(index.size() * 8);
-    uint32_t *d_st = (uint32_t *)G.C->dev_alloc(ns * 4);
-    hipError_t e = hipMemcpyAsync(d_sh, shards.data(), ns * sizeof(ZgShard), hipMemcpyHostToDevice, G.s);
-    if (e == hipSuccess) e = launch_shard_index(d_sh, (uint32_t)ns, spec, d_idx, d_st, 0, G.s);
-    if (e == hipSuccess) e = hipMemcpyAsync(index.data(), d_idx, index.size() * 8, hipMemcpyDeviceToHost, G.s);
-    if (e == hipSuccess) e = hipMemcpyAsync(sst.data(), d_st, ns * 4, hipMemcpyDeviceToHost, G.s);
-    if (e == hipSuccess) e = hipStreamSynchronize(G.s);
-    G.C->dev_free(d_sh);
-    G.C->dev_free(d_idx);
-    G.C->dev_free(d_st);
-    if (e != hipSuccess) throw HipFail{e, "nested shard indexes"};
-  }
-  std::vector<zgpu_chunk_desc> sub;
-  std::vector<uint64_t> owner;
-  for (uint64_t i = 0; i < n; i++) {
-    const zgpu_chunk_desc &D = descs[i];
-    if (status[i] || sel_volume(D, nd) == 0) continue;
-    const uint64_t sh = shard_of[i];
-    if (sh != UINT64_MAX && sst[sh]) {
-      status[i] = (int32_t)sst[sh];
-      continue;
-    }
-    uint64_t lo[ZG_MAXD], hi[ZG_MAXD], idx[ZG_MAXD];
-    for (uint32_t d = 0; d < nd; d++) {
-      cps[d] = D.chunk_shape[d] / ms[d];
-      lo[d] = D.sel_start[d] / ms[d];
-      hi[d] = (D.sel_start[d] + D.sel_shape[d] - 1) / ms[d] + 1;
-      idx[d] = lo[d];
-    }
-    for (;;) {  // every intersecting middle shard, C order
-      zgpu_chunk_desc M{};
-      uint64_t lin = 0;
-      for (uint32_t d = 0; d < nd; d++) {
-        lin = lin * cps[d] + idx[d];
-        const uint64_t cs = idx[d] * ms[d], ce = cs + ms[d];
-        const uint64_t s0 = std::max(D.sel_start[d], cs), s1 = std::min(D.sel_start[d] + D.sel_shape[d], ce);
-        M.chunk_shape[d] = ms[d];
-        M.sel_start[d] = s0 - cs;
-        M.sel_shape[d] = s1 - s0;
-        M.out_start[d] = D.out_start[d] + (s0 - D.sel_start[d]);
-      }
-      bool oob = false;
-      if (sh != UINT64_MAX) {
-        const uint64_t off = index[(sh * n_inner + lin) * 2], size = index[(sh * n_inner + lin) * 2 + 1];
-        if (!(off == ~0ull && size == ~0ull)) {
-          if (off > D.enc_len || size > D.enc_len - off) oob = true;
-          M.enc = (const uint8_t *)D.enc + off;
-          M.enc_len = size;
-        }
-      }
-      if (oob) {  // sharding_codec.rs: an inner chunk outside the shard
-        status[i] = ZGPU_SHARD_INDEX_OOB;
-      } else {
-        sub.push_back(M);
-        owner.push_back(i);
-      }
-      int d = (int)nd - 1;
-      for (; d >= 0; d--) {
-        if (++idx[d] < hi[d]) break;
-        idx[d] = lo[d];
-      }
-      if (d < 0 || oob) break;
-    }
-  }
-  run_sub(G, top.a2b.inner, sub, owner, status);
-}
-
-// Transpose codecs before a sharding_indexed the fused plan does not take (bytes->bytes codecs after
-// it, or shards with codecs around them / nested deeper below it). zarrs decodes the sharding codec
-// on the encoded (transposed) shape, then the transposes (codec_chain.rs:592-646, transpose_codec.rs:
-// 264-281), and a partial read asks the sharding partial decoder for the selection's box in the
-// encoded frame (transpose_codec_partial.rs). Here every descriptor's selection is decoded by the
-// chain without its transposes, in the encoded frame, into its own box of a device buffer (boxes
-// stacked along axis 0); the boxes are packed compact (k_box_copy) and then decoded as the leaf chunks
-// of [transposes, bytes(native)], which transposes and scatters them into the output in one fused pass.
-static void transposed_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
-                               uint64_t n, int32_t *status) {
-  const Chain &top = *chain;
-  const uint32_t nd = G.nd, es = top.es;
-  uint32_t m[ZG_MAXD];
-  composed_axes(top, nd, m);  // encoded axis a <-> decoded axis m[a]
-  auto bare = std::make_shared<Chain>(top);
-  bare->a2a.clear();
-  auto tr = std::make_shared<Chain>(top);
-  tr->b2b.clear();
-  tr->a2b = Codec{};
-  tr->a2b.kind = CodecKind::Bytes;
-  tr->a2b.name = "bytes";
-  tr->a2b.big_endian = false;  // the decoded elements are native (little-endian) already
-  std::vector<zgpu_chunk_desc> enc_descs;
-  std::vector<uint64_t> owner, row0;
-  uint64_t stacked[ZG_MAXD] = {0};
-  for (uint64_t i = 0; i < n; i++) {
-    const zgpu_chunk_desc &D = descs[i];
-    if (!desc_geometry_ok(D, nd, G.out_shape)) {
-      status[i] = ZGPU_INVALID_ARGUMENT;
-      continue;
-    }
-    if (sel_volume(D, nd) == 0) continue;
-    zgpu_chunk_desc E = D;
-    for (uint32_t a = 0; a < nd; a++) {
-      E.chunk_shape[a] = D.chunk_shape[m[a]];
-      E.sel_start[a] = D.sel_start[m[a]];
-      E.sel_shape[a] = D.sel_shape[m[a]];
-      E.out_start[a] = 0;
-    }
-    E.out_start[0] = stacked[0];
-    row0.push_back(stacked[0]);
-    stacked[0] += E.sel_shape[0];
-    for (uint32_t a = 1; a < nd; a++) stacked[a] = std::max(stacked[a], E.sel_shape[a]);
-    enc_descs.push_back(E);
-    owner.push_back(i);
-  }
-  if (enc_descs.empty()) return;
-  uint64_t stacked_bytes = es;
-  for (uint32_t a = 0; a < nd; a++) stacked_bytes *= stacked[a];
-  uint64_t pack_bytes = 0;
-  std::vector<uint64_t> pack_off(enc_descs.size());
-  for (size_t k = 0; k < enc_descs.size(); k++) {
-    pack_off[k] = pack_bytes;
-    pack_bytes += sel_volume(enc_descs[k], nd) * es;
-  }
-  uint8_t *T = (uint8_t *)G.C->dev_alloc(stacked_bytes);
-  uint8_t *Pk = nullptr;
-  try {
-    // the encoded-frame boxes
-    GeneralCall G1{G.C, G.validate, nd, T, stacked, G.flags, G.s, {}};
-    std::vector<int32_t> st(enc_descs.size(), 0);
-    const bool had_detail = g_size_detail.valid;
-    decode_general(G1, bare, enc_descs.data(), enc_descs.size(), st.data());
-    if (!had_detail && g_size_detail.valid) g_size_detail.desc = owner[g_size_detail.desc];
-    Pk = (uint8_t *)G.C->dev_alloc(std::max<uint64_t>(pack_bytes, 1));
-    std::vector<zgpu_chunk_desc> leaf;
-    std::vector<uint64_t> leaf_owner;
-    for (size_t k = 0; k < enc_descs.size(); k++) {
-      const uint64_t i = owner[k];
-      if (st[k]) {
-        status[i] = st[k];
-        continue;
-      }
-      uint64_t org[ZG_MAXD] = {0};
-      org[0] = row0[k];
-      pack_box(T, nd, stacked, org, enc_descs[k].sel_shape, es, Pk, pack_off[k], G.s);
-      zgpu_chunk_desc L{};
-      L.enc = Pk + pack_off[k];
-      L.enc_len = sel_volume(enc_descs[k], nd) * es;
-      for (uint32_t a = 0; a < nd; a++) {
-        L.chunk_shape[a] = L.sel_shape[a] = descs[i].sel_shape[a];
-        L.sel_start[a] = 0;
-        L.out_start[a] = descs[i].out_start[a];
-      }
-      leaf.push_back(L);
-      leaf_owner.push_back(i);
-    }
-    run_sub(G, tr, leaf, leaf_owner, status);
-  } catch (...) {
-    G.C->dev_free(T);
-    G.C->dev_free(Pk);
-    throw;
-  }
-  G.C->dev_free(T);
-  G.C->dev_free(Pk);
-}
-
-// The chain without its value codecs (numcodecs.fixedscaleoffset, bitround), at every sharding level;
-// `steps` receives them in encode order. They work element by element, so they commute with
-// chunking, sharding, transposes and selection: what the stripped chain decodes, in the innermost
-// encoded data type, is the selection before the value codecs' decode.
-static std::shared_ptr<Chain> strip_value_codecs(const Chain &c, std::vector<Codec> &steps) {
-  auto r = std::make_shared<Chain>(c);
-  r->a2a.clear();
-  for (const Codec &k : c.a2a) {
-    if (is_value_codec(k.kind)) steps.push_back(k);
-    else r->a2a.push_back(k);
-  }
-  if (c.a2b.kind == CodecKind::Sharding) r->a2b.inner = strip_value_codecs(*c.a2b.inner, steps);
-  return r;
-}
-
-// Every level of a stripped chain bound to the innermost encoded data type and fill value.
-static void retype_stripped(Chain &c, const Chain &original) {
-  const Chain *leaf = &original;
-  while (leaf->a2b.kind == CodecKind::Sharding) leaf = leaf->a2b.inner.get();
-  for (Chain *l = &c;; l = l->a2b.inner.get()) {
-    l->es = l->enc_es = leaf->enc_es;
-    l->comp = l->enc_comp = leaf->enc_comp;
-    l->data_type = l->enc_data_type = leaf->enc_data_type;
-    std::memcpy(l->fill, leaf->enc_fill, 16);
-    std::memcpy(l->enc_fill, leaf->enc_fill, 16);
-    if (l->a2b.kind != CodecKind::Sharding) break;
-  }
-}
-
-static uint32_t mantissa_bits_of(uint32_t vt) {
-  return vt == VT_F16 ? 10 : vt == VT_BF16 ? 7 : vt == VT_F32 ? 23 : vt == VT_F64 ? 52 : 0;
-}
-
-// n elements through the value codecs' decode (`steps` in encode order, run backwards) from `in`, in
-// the innermost encoded type, into `out` (must not be `in`), in the decoded type. bitround decodes
-// as the identity. Temporaries go to `owned`. Enqueues only.
-static void value_decode_elements(zgpu_ctx *C, const std::vector<Codec> &steps, const uint8_t *in, uint8_t *out,
-                                  uint64_t n, uint32_t es_out, std::vector<void *> &owned, hipStream_t s) {
-  std::vector<const Codec *> fso;
-  for (size_t j = steps.size(); j-- > 0;)
-    if (steps[j].kind == CodecKind::FixedScaleOffset) fso.push_back(&steps[j]);
-  if (fso.empty()) {
-    if (n) HIPCHK(hipMemcpyAsync(out, in, n * es_out, hipMemcpyDeviceToDevice, s));
-    return;
-  }
-  const uint8_t *cur = in;
-  for (size_t j = 0; j < fso.size(); j++) {
-    const Codec &k = *fso[j];
-    uint8_t *dst = out;
-    if (j + 1 < fso.size()) {
-      dst = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n * value_type_size(k.vt_dec), 1));
-      owned.push_back(dst);
-    }
-    HIPCHK(launch_fso_decode(k.vt_enc, k.vt_dec, cur, dst, n, k.fso_offset, k.fso_scale, k.fso_astype ? 1 : 0, s));
-    cur = dst;
-  }
-}
-
-// n elements through the value codecs' encode, `in` (decoded type) to a new device array in the
-// innermost encoded type (returned, in `owned`).
-static uint8_t *value_encode_elements(zgpu_ctx *C, const std::vector<Codec> &steps, const uint8_t *in, uint64_t n,
-                                      std::vector<void *> &owned, hipStream_t s) {
-  const uint8_t *cur = in;
-  uint8_t *dst = nullptr;
-  for (const Codec &k : steps) {
-    dst = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n * value_type_size(k.vt_enc), 1));
-    owned.push_back(dst);
-    if (k.kind == CodecKind::FixedScaleOffset)
-      HIPCHK(launch_fso_encode(k.vt_dec, k.vt_enc, cur, dst, n, k.fso_offset, k.fso_scale, k.fso_astype ? 1 : 0, s));
-    else
-      HIPCHK(launch_bitround(value_type_size(k.vt_dec), mantissa_bits_of(k.vt_dec), k.keepbits, cur, dst, n, s));
-    cur = dst;
-  }
-  return dst;
-}
-
-// Chains with value codecs, before sharding_indexed, inside its inner chains, or both. The chain
-// without them, retyped to the innermost encoded data type and fill value, decodes the callers'
-// selections into a device buffer of that type (so a missing chunk or inner chunk holds the encoded
-// fill value, as in zarrs); k_fso_decode then converts the buffer into the output: one extra pass over
-// the data when the descriptors cover the output (the converted buffer is the output), and through the
-// stacked boxes of transposed_general otherwise. Only bitround: its decode is the identity, so the
-// stripped chain writes the output itself.
-static void value_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
-                          uint64_t n, int32_t *status) {
-  const Chain &top = *chain;
-  const uint32_t nd = G.nd;
-  std::vector<Codec> steps;
-  auto bare = strip_value_codecs(top, steps);
-  retype_stripped(*bare, top);
-  bool any_fso = false;
-  for (const Codec &k : steps) any_fso = any_fso || k.kind == CodecKind::FixedScaleOffset;
-  if (!any_fso) {
-    decode_general(G, bare, descs, n, status);
-    return;
-  }
-  const uint32_t es_e = bare->es, es_d = top.es;
-  std::vector<void *> owned;
-  auto release = [&]() {
-    (void)hipStreamSynchronize(G.s);
-    for (void *p : owned) G.C->dev_free(p);
-    owned.clear();
-  };
-  try {
-    bool geometry = true;
-    uint64_t covered = 0, out_elems = 1;
-    for (uint64_t i = 0; i < n; i++) {
-      geometry = geometry && desc_geometry_ok(descs[i], nd, G.out_shape);
-      covered += sel_volume(descs[i], nd);
-    }
-    for (uint32_t d = 0; d < nd; d++) out_elems *= G.out_shape[d];
-    if (geometry && covered == out_elems) {
-      // the (disjoint) selections tile the output: decode into its image in the encoded type, convert
-      uint8_t *T = (uint8_t *)G.C->dev_alloc(std::max<uint64_t>(out_elems * es_e, 1));
-      owned.push_back(T);
-      GeneralCall G1{G.C, G.validate, nd, T, G.out_shape, G.flags, G.s, {}};
-      decode_general(G1, bare, descs, n, status);
-      value_decode_elements(G.C, steps, T, G.out, out_elems, es_d, owned, G.s);
-      release();
-      return;
-    }
-    // every selection into its own box of a stacked buffer, packed compact, converted, then scattered
-    // as the leaf chunks of [bytes(native)] in the decoded type
-    auto plain = std::make_shared<Chain>(top);
-    plain->a2a.clear();
-    plain->b2b.clear();
-    plain->a2b = Codec{};
-    plain->a2b.kind = CodecKind::Bytes;
-    plain->a2b.name = "bytes";
-    plain->enc_es = top.es;
-    plain->enc_comp = top.comp;
-    plain->enc_data_type = top.data_type;
-    std::memcpy(plain->enc_fill, top.fill, 16);
-    std::vector<zgpu_chunk_desc> enc_descs;
-    std::vector<uint64_t> owner, row0;
-    uint64_t stacked[ZG_MAXD] = {0};
-    for (uint64_t i = 0; i < n; i++) {
-      const zgpu_chunk_desc &D = descs[i];
-      if (!desc_geometry_ok(D, nd, G.out_shape)) {
-        status[i] = ZGPU_INVALID_ARGUMENT;
-        continue;
-      }
-      if (sel_volume(D, nd) == 0) continue;
-      zgpu_chunk_desc E = D;
-      for (uint32_t a = 0; a < nd; a++) E.out_start[a] = 0;
-      E.out_start[0] = stacked[0];
-      row0.push_back(stacked[0]);
-      stacked[0] += E.sel_shape[0];
-      for (uint32_t a = 1; a < nd; a++) stacked[a] = std::max(stacked[a], E.sel_shape[a]);
-      enc_descs.push_back(E);
-      owner.push_back(i);
-    }
-    if (enc_descs.empty()) return;
-    uint64_t stacked_elems = 1, pack_elems = 0;
-    for (uint32_t a = 0; a < nd; a++) stacked_elems *= stacked[a];
-    std::vector<uint64_t> pack_off(enc_descs.size());
-    for (size_t k = 0; k < enc_descs.size(); k++) {
-      pack_off[k] = pack_elems;
-      pack_elems += sel_volume(enc_descs[k], nd);
-    }
-    uint8_t *T = (uint8_t *)G.C->dev_alloc(stacked_elems * es_e);
-    owned.push_back(T);
-    GeneralCall G1{G.C, G.validate, nd, T, stacked, G.flags, G.s, {}};
-    std::vector<int32_t> st(enc_descs.size(), 0);
-    const bool had_detail = g_size_detail.valid;
-    decode_general(G1, bare, enc_descs.data(), enc_descs.size(), st.data());
-    if (!had_detail && g_size_detail.valid) g_size_detail.desc = owner[g_size_detail.desc];
-    uint8_t *PkE = (uint8_t *)G.C->dev_alloc(pack_elems * es_e);
-    owned.push_back(PkE);
-    uint8_t *PkD = (uint8_t *)G.C->dev_alloc(pack_elems * es_d);
-    owned.push_back(PkD);
-    std::vector<zgpu_chunk_desc> leaf;
-    std::vector<uint64_t> leaf_owner;
-    for (size_t k = 0; k < enc_descs.size(); k++) {
-      const uint64_t i = owner[k];
-      if (st[k]) {
-        status[i] = st[k];
-        continue;
-      }
-      uint64_t org[ZG_MAXD] = {0};
-      org[0] = row0[k];
-      pack_box(T, nd, stacked, org, enc_descs[k].sel_shape, es_e, PkE, pack_off[k] * es_e, G.s);
-      zgpu_chunk_desc L{};
-      L.enc = PkD + pack_off[k] * es_d;
-      L.enc_len = sel_volume(enc_descs[k], nd) * es_d;
-      for (uint32_t a = 0; a < nd; a++) {
-        L.chunk_shape[a] = L.sel_shape[a] = descs[i].sel_shape[a];
-        L.sel_start[a] = 0;
-        L.out_start[a] = descs[i].out_start[a];
-      }
-      leaf.push_back(L);
-      leaf_owner.push_back(i);
-    }
-    value_decode_elements(G.C, steps, PkE, PkD, pack_elems, es_d, owned, G.s);
-    run_sub(G, plain, leaf, leaf_owner, status);
-  } catch (...) {
-    release();
-    throw;
-  }
-  release();
-}
-
-// packbits as the array->bytes codec (unsharded): its chunks are not element-aligned, so whole chunks
-// of [bytes(uint8), bytes->bytes codecs...] over the packed length are decoded into a device buffer
-// (which checks the packed length: DECODED_SIZE_MISMATCH), k_unpackbits expands them into native
-// elements (and checks the padding byte: CORRUPT_STREAM), and those are the leaf chunks of
-// [array->array codecs..., bytes(native)] with the callers' selections.
-static void packbits_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
-                             uint64_t n, int32_t *status) {
-  const Chain &top = *chain;
-  const Codec &pb = top.a2b;
-  const uint32_t nd = G.nd, es = top.enc_es;
-  uint64_t nelem = 1;
-  for (uint32_t d = 0; d < nd; d++) nelem *= descs[0].chunk_shape[d];
-  const uint64_t packed = packbits_size(pb, nelem);
-  const uint64_t ppitch = ((packed + 15) & ~(uint64_t)15) + 16, upitch = (nelem * es + 15) & ~(uint64_t)15;
-  auto packed_chain = std::make_shared<Chain>();
-  packed_chain->es = packed_chain->comp = packed_chain->enc_es = packed_chain->enc_comp = 1;
-  packed_chain->data_type = packed_chain->enc_data_type = "uint8";
-  packed_chain->a2b.kind = CodecKind::Bytes;
-  packed_chain->a2b.name = "bytes";
-  packed_chain->b2b = top.b2b;
-  auto leaf_chain = std::make_shared<Chain>(top);
-  leaf_chain->b2b.clear();
-  leaf_chain->a2b = Codec{};
-  leaf_chain->a2b.kind = CodecKind::Bytes;
-  leaf_chain->a2b.name = "bytes";
-  std::vector<zgpu_chunk_desc> pk;  // 1-D descriptors of the packed chunks, slot j of the buffer
-  std::vector<uint64_t> pk_owner;
-  for (uint64_t i = 0; i < n; i++) {
-    const zgpu_chunk_desc &D = descs[i];
-    if (!desc_geometry_ok(D, nd, G.out_shape)) {
-      status[i] = ZGPU_INVALID_ARGUMENT;
-      continue;
-    }
-    if (!D.enc || sel_volume(D, nd) == 0) continue;  // a missing chunk: the leaf chain fills it
-    zgpu_chunk_desc E{};
-    E.enc = D.enc;
-    E.enc_len = D.enc_len;
-    E.chunk_shape[0] = E.sel_shape[0] = packed;
-    E.out_start[0] = pk.size() * ppitch;
-    pk.push_back(E);
-    pk_owner.push_back(i);
-  }
-  const uint64_t m = pk.size();
-  uint8_t *B = nullptr, *U = nullptr;
-  uint64_t *d_tab = nullptr;
-  uint32_t *d_st = nullptr;
-  auto release = [&]() {
-    (void)hipStreamSynchronize(G.s);
-    G.C->dev_free(B);
-    G.C->dev_free(U);
-    G.C->dev_free(d_tab);
-    G.C->dev_free(d_st);
-  };
-  try {
-    std::vector<int32_t> st(m, 0);
-    std::vector<uint64_t> slot(n, UINT64_MAX);
-    if (m) {
-      const uint64_t b_shape[1] = {m * ppitch};
-      B = (uint8_t *)G.C->dev_alloc(m * ppitch);
-      U = (uint8_t *)G.C->dev_alloc(std::max<uint64_t>(m * upitch, 1));
-      GeneralCall G1{G.C, G.validate, 1, B, b_shape, G.flags, G.s, {}};
-      const bool had_detail = g_size_detail.valid;
-      decode_general(G1, packed_chain, pk.data(), m, st.data());
-      if (!had_detail && g_size_detail.valid) g_size_detail.desc = pk_owner[g_size_detail.desc];
-      std::vector<uint64_t> tab;
-      std::vector<uint64_t> ok;
-      for (uint64_t j = 0; j < m; j++)
-        if (!st[j]) ok.push_back(j);
-      for (uint64_t j : ok) tab.push_back((uint64_t)(B + j * ppitch));
-      for (uint64_t j : ok) tab.push_back((uint64_t)(U + j * upitch));
-      if (!ok.empty()) {
-        d_tab = (uint64_t *)G.C->dev_alloc(tab.size() * 8);
-        d_st = (uint32_t *)G.C->dev_alloc(ok.size() * 4);
-        HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, G.s));
-        HIPCHK(hipMemsetAsync(d_st, 0, ok.size() * 4, G.s));
-        ZgPackBits P{};
-        P.nelem = nelem;
-        P.packed_len = packed;
-        P.ncomp = pb.pb_ncomp;
-        P.comp_bytes = es / pb.pb_ncomp;
-        P.first = pb.pb_first;
-        P.ext = pb.pb_last - pb.pb_first + 1;
-        P.sign = pb.pb_signed ? 1 : 0;
-        P.padding = (uint32_t)pb.pb_padding;
-        HIPCHK(launch_unpackbits(d_tab, d_st, (uint32_t)ok.size(), P, G.s));
-        std::vector<uint32_t> ust(ok.size());
-        HIPCHK(hipMemcpyAsync(ust.data(), d_st, ok.size() * 4, hipMemcpyDeviceToHost, G.s));
-        HIPCHK(hipStreamSynchronize(G.s));
-        for (size_t k = 0; k < ok.size(); k++) st[ok[k]] = (int32_t)ust[k];
-      }
-      for (uint64_t j = 0; j < m; j++) {
-        if (st[j]) status[pk_owner[j]] = st[j];
-        else slot[pk_owner[j]] = j;
-      }
-    }
-    std::vector<zgpu_chunk_desc> leaf;
-    std::vector<uint64_t> leaf_owner;
-    for (uint64_t i = 0; i < n; i++) {
-      if (status[i] || sel_volume(descs[i], nd) == 0) continue;
-      zgpu_chunk_desc L = descs[i];
-      if (slot[i] != UINT64_MAX) {
-        L.enc = U + slot[i] * upitch;
-        L.enc_len = nelem * es;
-      } else {
-        L.enc = nullptr;
-        L.enc_len = 0;
-      }
-      leaf.push_back(L);
-      leaf_owner.push_back(i);
-    }
-    run_sub(G, leaf_chain, leaf, leaf_owner, status);
-  } catch (...) {
-    release();
-    throw;
-  }
-  release();
-}
-
-static void decode_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
-                           uint64_t n, int32_t *status) {
-  for (uint64_t i = 0; i < n; i++) status[i] = 0;
-  if (!uniform_shapes(descs, n, G.nd)) {  // one plan per chunk shape
-    std::vector<char> done(n, 0);
-    for (uint64_t i = 0; i < n; i++) {
-      if (done[i]) continue;
-      std::vector<zgpu_chunk_desc> sub;
-      std::vector<uint64_t> owner;
-      for (uint64_t j = i; j < n; j++)
-        if (!done[j] && same_shape(descs[i], descs[j], G.nd)) {
-          sub.push_back(descs[j]);
-          owner.push_back(j);
-          done[j] = 1;
-        }
-      run_sub(G, chain, sub, owner, status);
-    }
-    return;
-  }
-  const Chain &top = *chain;
-  if (chain_has_value_codec(top) || top.a2b.kind == CodecKind::PackBits) {
-    if (!n) return;
-    if (chain_has_value_codec(top)) value_general(G, chain, descs, n, status);
-    else packbits_general(G, chain, descs, n, status);
-    return;
-  }
-  if (fused_plannable(top)) {
-    std::unique_ptr<zgpu_plan> P(plan_new(G.C, chain, G.validate, G.nd, descs, n, G.out_shape, G.flags));
-    plan_upload(*P, G.s);
-    plan_enqueue(*P, G.out, G.s);
-    plan_statuses(*P, status, G.s);
-    return;
-  }
-  if (!top.a2a.empty()) transposed_general(G, chain, descs, n, status);
-  else if (!top.b2b.empty()) predecode_shards(G, chain, descs, n, status);
-  else nested_host(G, chain, descs, n, status);
-}
-
-// ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-#define ABI_GUARD_BEGIN try {
-#define ABI_GUARD_END                                                                          \
-  }                                                                                            \
-  catch (const ChainError &e) {                                                                \
-    return set_err(e.status, e.msg);                                                           \
-  }                                                                                            \
-  catch (const HipFail &e) {                                                                   \
-    return set_err(ZGPU_HIP_ERROR, std::string(e.what) + ": " + hipGetErrorString(e.e));       \
-  }                                                                                            \
-  catch (const std::exception &e) {                                                            \
-    return set_err(ZGPU_INVALID_ARGUMENT, e.what());                                           \
-  }
-
 // array_read_ops_common.rs:20-109: subset -> intersecting chunks -> one descriptor per chunk, in
 // C order of the chunk grid; lins[k] = descriptor k's C-order linear chunk-grid index.
 // Returns ZGPU_OK, -1 for an empty subset (nothing to do), or an error status.
@@ -2536,16 +1244,18 @@ static bool decode_pipelined(zgpu_chain *ch, Lane *LN, uint32_t nd, const zgpu_c
       range_of[i] = R.size() - 1;
     }
   }
-  uint8_t *enc_dev = (uint8_t *)C->dev_alloc(total ? total : 1);
-  uint8_t *dout = (uint8_t *)C->dev_alloc(out_shape[0] * row_bytes);
-  std::vector<hipEvent_t> ev(2 * groups.size(), nullptr);
+  Scratch sc(C, s);
+  uint8_t *enc_dev = sc.dev<uint8_t>(total ? total : 1);
+  uint8_t *dout = sc.dev<uint8_t>(out_shape[0] * row_bytes);
+  struct Events {  // destroyed after the plans below, before the buffers above go back
+    std::vector<hipEvent_t> v;
+    ~Events() {
+      for (hipEvent_t e : v)
+        if (e) (void)hipEventDestroy(e);
+    }
+  } events{std::vector<hipEvent_t>(2 * groups.size(), nullptr)};
+  std::vector<hipEvent_t> &ev = events.v;
   std::vector<std::unique_ptr<zgpu_plan>> plans(groups.size());
-  auto cleanup = [&]() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    C->dev_free(enc_dev);
-    C->dev_free(dout);
-  };
   try {
     for (hipEvent_t &e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (size_t g = 0; g < groups.size(); g++) {
@@ -2590,13 +1300,9 @@ static bool decode_pipelined(zgpu_chain *ch, Lane *LN, uint32_t nd, const zgpu_c
     }
     HIPCHK(hipStreamSynchronize(LN->copy[1]));
   } catch (...) {
-    (void)hipDeviceSynchronize();
-    plans.clear();
-    cleanup();
+    (void)hipDeviceSynchronize();  // the copy streams too
     throw;
   }
-  plans.clear();
-  cleanup();
   return true;
 }
 
@@ -2606,20 +1312,14 @@ static bool decode_pipelined(zgpu_chain *ch, Lane *LN, uint32_t nd, const zgpu_c
 // merged into ranges; pinned ranges are DMA'd directly (one copy per range), pageable ones through
 // the pinned staging slabs. local[i].enc is rewritten to descriptor i's device copy.
 struct HostStage {
-  zgpu_ctx *C;
+  Scratch sc;  // the staging buffer and slabs, and the call's other temporaries on the same stream
   uint8_t *enc = nullptr, *pin = nullptr;
   static constexpr uint64_t slab = 64ull << 20;
-  explicit HostStage(zgpu_ctx *c) : C(c) {}
-  ~HostStage() {
-    C->dev_free(enc);
-    C->host_free(pin);
-  }
+  HostStage(zgpu_ctx *c, hipStream_t s) : sc(c, s) {}
   uint8_t *stage() {  // 2 slabs of pinned staging, only for pageable host buffers
-    if (!pin) pin = (uint8_t *)C->host_alloc(2 * slab);
+    if (!pin) pin = sc.pinned<uint8_t>(2 * slab);
     return pin;
   }
-  HostStage(const HostStage &) = delete;
-  HostStage &operator=(const HostStage &) = delete;
 };
 
 static void stage_host_inputs(HostStage &H, const zgpu_chunk_desc *descs, uint64_t n,
@@ -2648,7 +1348,7 @@ static void stage_host_inputs(HostStage &H, const zgpu_chunk_desc *descs, uint64
     range_of[i] = ranges.size() - 1;
   }
   if (!total) return;
-  H.enc = (uint8_t *)H.C->dev_alloc(total);
+  H.enc = H.sc.dev<uint8_t>(total);
   bool pinned = true;
   for (const HostRange &r : ranges)
     if (!host_is_pinned(r.src) || !host_is_pinned(r.src + r.len - 1)) {
@@ -2668,7 +1368,7 @@ static uint64_t covered_volume(const zgpu_chunk_desc *descs, uint64_t n, uint32_
   return covered;
 }
 
-static uint64_t volume(const uint64_t *shape, uint32_t nd) {
+uint64_t volume(const uint64_t *shape, uint32_t nd) {
   uint64_t v = 1;
   for (uint32_t d = 0; d < nd; d++) v *= shape[d];
   return v;
@@ -2711,7 +1411,7 @@ static int decode_call(zgpu_chain *ch, Lane *LN, hipStream_t s, uint32_t nd, con
         decode_pipelined(ch, LN, nd, descs, n, (uint8_t *)V.base, V.shape, flags, status, s, rc))
       return rc;
   }
-  HostStage H(C);
+  HostStage H(C, s);
   std::vector<zgpu_chunk_desc> local;
   const zgpu_chunk_desc *dd = descs;
   if (!(flags & ZGPU_ENC_DEVICE)) {
@@ -2750,19 +1450,12 @@ static int decode_call(zgpu_chain *ch, Lane *LN, hipStream_t s, uint32_t nd, con
   // window no descriptor covers keep the caller's bytes (the regions are disjoint,
   // ArrayBytesFixedDisjointView, so equal volumes mean full coverage and no upload)
   const uint64_t out_bytes = out_elems * es;
-  uint8_t *dout = (uint8_t *)C->dev_alloc(out_bytes ? out_bytes : 1);
+  uint8_t *dout = H.sc.dev<uint8_t>(out_bytes ? out_bytes : 1);
   const BoxRuns R = box_runs(nd, V.array_shape, V.start, V.shape, es);
-  int rc = 0;
-  try {
-    if (covered_volume(descs, n, nd) != out_elems)
-      HIPCHK(h2d_box(R, dout, (const uint8_t *)V.base, H.stage(), HostStage::slab, host_copy_threads(), s));
-    rc = decode_device(ch, nd, dd, n, dout, V.shape, flags, status, s);
-    HIPCHK(d2h_box(R, (uint8_t *)V.base, dout, H.stage(), HostStage::slab, host_copy_threads(), s));
-  } catch (...) {
-    C->dev_free(dout);
-    throw;
-  }
-  C->dev_free(dout);
+  if (covered_volume(descs, n, nd) != out_elems)
+    HIPCHK(h2d_box(R, dout, (const uint8_t *)V.base, H.stage(), HostStage::slab, host_copy_threads(), s));
+  const int rc = decode_device(ch, nd, dd, n, dout, V.shape, flags, status, s);
+  HIPCHK(d2h_box(R, (uint8_t *)V.base, dout, H.stage(), HostStage::slab, host_copy_threads(), s));
   return rc;
 }
 
@@ -2895,7 +1588,11 @@ static void co_run(CoBatch &B, Lane *LN) {
       owner.push_back({(uint32_t)k, i});
     }
   }
-  HostStage H(C);
+  HostStage H(C, s);
+  struct Drain {  // the pack and D2H below move to the high-priority stream: s is then that one, and a
+    hipStream_t &s;  // failure must not return dout / dpack (H's) with work still queued on it
+    ~Drain() { (void)hipStreamSynchronize(s); }
+  } drain{s};
   std::vector<zgpu_chunk_desc> local;
   co_trace("batch-start", B.id, B.calls.size(), all.size());
   stage_host_inputs(H, all.data(), all.size(), local, s);
@@ -2908,119 +1605,110 @@ static void co_run(CoBatch &B, Lane *LN) {
     c->pack_off = pack_bytes;
     pack_bytes += volume(c->V.shape, nd) * es;
   }
-  uint8_t *dout = (uint8_t *)C->dev_alloc(stacked_bytes ? stacked_bytes : 1);
-  uint8_t *dpack = nullptr;
-  try {
-    std::vector<int32_t> ast(all.size(), 0);
-    decode_device(ch, nd, local.data(), local.size(), dout, stacked, c0.flags, ast.data(), s);
-    co_trace("decode-done", B.id);
-    const SizeDetail sd = g_size_detail;
-    for (size_t j = 0; j < all.size(); j++) st[owner[j].first][owner[j].second] = ast[j];
-    if (sd.valid && sd.desc < owner.size()) {
-      CoCall &c = *B.calls[owner[sd.desc].first];
-      c.sd = sd;
-      c.sd.desc = owner[sd.desc].second;
+  uint8_t *dout = H.sc.dev<uint8_t>(stacked_bytes ? stacked_bytes : 1);
+  std::vector<int32_t> ast(all.size(), 0);
+  decode_device(ch, nd, local.data(), local.size(), dout, stacked, c0.flags, ast.data(), s);
+  co_trace("decode-done", B.id);
+  const SizeDetail sd = g_size_detail;
+  for (size_t j = 0; j < all.size(); j++) st[owner[j].first][owner[j].second] = ast[j];
+  if (sd.valid && sd.desc < owner.size()) {
+    CoCall &c = *B.calls[owner[sd.desc].first];
+    c.sd = sd;
+    c.sd.desc = owner[sd.desc].second;
+  }
+  // The pack kernels and the D2H run on a high-priority stream: the other lanes' decodes hold the
+  // CUs with long-running waves, and a normal-priority pack kernel queued behind them waited for
+  // their slots (trace: 60 MB packs taking 20+ ms). ZGPU_CO_HIPRIO=0: the lane's own stream.
+  static const bool hiprio = [] {
+    const char *e = std::getenv("ZGPU_CO_HIPRIO");
+    return !e || std::atoi(e) != 0;
+  }();
+  if (hiprio) {
+    if (!LN->out_hi) {
+      int least = 0, greatest = 0;
+      HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+      HIPCHK(hipStreamCreateWithPriority(&LN->out_hi, hipStreamNonBlocking, greatest));
     }
-    // The pack kernels and the D2H run on a high-priority stream: the other lanes' decodes hold the
-    // CUs with long-running waves, and a normal-priority pack kernel queued behind them waited for
-    // their slots (trace: 60 MB packs taking 20+ ms). ZGPU_CO_HIPRIO=0: the lane's own stream.
-    static const bool hiprio = [] {
-      const char *e = std::getenv("ZGPU_CO_HIPRIO");
+    HIPCHK(hipStreamSynchronize(s));  // (decode_device has read its statuses back: a no-op)
+    s = LN->out_hi;
+  }
+  // pack: a window whose trailing extents are the stacked ones is already compact in place
+  bool compact = true;
+  for (CoCall *c : B.calls)
+    for (uint32_t d = 1; d < nd; d++)
+      if (c->V.shape[d] != stacked[d]) compact = false;
+  std::vector<BoxRuns> boxes;
+  bool rect = false;  // every window a 3-D box: packed by the copy engines, no kernel
+  if (!compact) {
+    static const bool rect_on = [] {
+      const char *e = std::getenv("ZGPU_CO_PACK_RECT");
       return !e || std::atoi(e) != 0;
     }();
-    if (hiprio) {
-      if (!LN->out_hi) {
-        int least = 0, greatest = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(hipStreamCreateWithPriority(&LN->out_hi, hipStreamNonBlocking, greatest));
-      }
-      HIPCHK(hipStreamSynchronize(s));  // (decode_device has read its statuses back: a no-op)
-      s = LN->out_hi;
+    rect = rect_on;
+    for (size_t k = 0; k < B.calls.size(); k++) {
+      uint64_t org[ZG_MAXD] = {0};
+      org[0] = row0[k];
+      boxes.push_back(box_runs(nd, stacked, org, B.calls[k]->V.shape, es));
+      if (boxes.back().outer > 2) rect = false;
     }
-    // pack: a window whose trailing extents are the stacked ones is already compact in place
-    bool compact = true;
-    for (CoCall *c : B.calls)
-      for (uint32_t d = 1; d < nd; d++)
-        if (c->V.shape[d] != stacked[d]) compact = false;
-    std::vector<BoxRuns> boxes;
-    bool rect = false;  // every window a 3-D box: packed by the copy engines, no kernel
-    if (!compact) {
-      static const bool rect_on = [] {
-        const char *e = std::getenv("ZGPU_CO_PACK_RECT");
-        return !e || std::atoi(e) != 0;
-      }();
-      rect = rect_on;
-      for (size_t k = 0; k < B.calls.size(); k++) {
-        uint64_t org[ZG_MAXD] = {0};
-        org[0] = row0[k];
-        boxes.push_back(box_runs(nd, stacked, org, B.calls[k]->V.shape, es));
-        if (boxes.back().outer > 2) rect = false;
-      }
-    }
-    // power-of-two size classes (>= 64 MiB): batches of varying size reuse pooled pinned buffers
-    // instead of page-locking new ones
-    if (compact || rect) co_trace("packed", B.id, compact ? 0 : 2);
-    uint64_t cls = 64ull << 20;
-    while (cls < pack_bytes) cls <<= 1;
-    B.pack = (uint8_t *)C->host_alloc(cls);
-    co_trace("pack-alloc", B.id);
-    if (compact) {
-      if (pack_bytes) HIPCHK(hipMemcpyAsync(B.pack, dout, pack_bytes, hipMemcpyDeviceToHost, s));
-    } else if (rect) {
-      // Each caller's window straight from the stacked output into its place in the pinned pack as
-      // one pitched 3-D copy (DMA): a box-copy kernel queued while other lanes' decode waves hold the
-      // CUs waited for their slots (trace: pack median 5 ms at 8 lanes, 20 ms at 2 lanes with bigger
-      // batches), and the copy engines need none.
-      for (size_t k = 0; k < B.calls.size(); k++) {
-        const BoxRuns &R = boxes[k];
-        if (!R.n_runs) continue;
-        const uint64_t w = R.run_bytes;
-        const uint64_t h = R.outer >= 1 ? R.shape[R.outer - 1] : 1, depth = R.outer >= 2 ? R.shape[0] : 1;
-        const uint64_t pitch = R.outer >= 1 ? R.stride[R.outer - 1] : w;
-        const uint64_t sy = R.outer >= 2 ? R.stride[0] / pitch : h;
-        hipMemcpy3DParms p3{};
-        p3.srcPtr = make_hipPitchedPtr(dout + R.base, pitch, w, sy);
-        p3.dstPtr = make_hipPitchedPtr(B.pack + B.calls[k]->pack_off, w, w, h);
-        p3.extent = make_hipExtent(w, h, depth);
-        p3.kind = hipMemcpyDeviceToHost;
-        HIPCHK(hipMemcpy3DAsync(&p3, s));
-      }
-    } else {
-      dpack = (uint8_t *)C->dev_alloc(pack_bytes ? pack_bytes : 1);
-      for (size_t k = 0; k < B.calls.size(); k++) {
-        const BoxRuns &R = boxes[k];
-        ZgBoxCopy P{};
-        P.outer = R.outer;
-        for (uint32_t d = 0; d < R.outer; d++) {
-          P.shape[d] = R.shape[d];
-          P.src_stride[d] = R.stride[d];
-        }
-        uint64_t cs = R.run_bytes;  // compact strides of the outer axes
-        for (int d = (int)R.outer - 1; d >= 0; d--) {
-          P.dst_stride[d] = cs;
-          cs *= R.shape[d];
-        }
-        P.src_base = R.base;
-        P.dst_base = B.calls[k]->pack_off;
-        P.run_bytes = R.run_bytes;
-        P.n_runs = R.n_runs;
-        HIPCHK(launch_box_copy(dout, dpack, P, s));
-      }
-      if (co_tracing()) {
-        HIPCHK(hipStreamSynchronize(s));
-        co_trace("packed", B.id, 1);
-      }
-      if (pack_bytes) HIPCHK(hipMemcpyAsync(B.pack, dpack, pack_bytes, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    co_trace("d2h-done", B.id, pack_bytes);
-  } catch (...) {
-    C->dev_free(dout);
-    C->dev_free(dpack);
-    throw;
   }
-  C->dev_free(dout);
-  C->dev_free(dpack);
+  // power-of-two size classes (>= 64 MiB): batches of varying size reuse pooled pinned buffers
+  // instead of page-locking new ones
+  if (compact || rect) co_trace("packed", B.id, compact ? 0 : 2);
+  uint64_t cls = 64ull << 20;
+  while (cls < pack_bytes) cls <<= 1;
+  B.pack = (uint8_t *)C->host_alloc(cls);
+  co_trace("pack-alloc", B.id);
+  if (compact) {
+    if (pack_bytes) HIPCHK(hipMemcpyAsync(B.pack, dout, pack_bytes, hipMemcpyDeviceToHost, s));
+  } else if (rect) {
+    // Each caller's window straight from the stacked output into its place in the pinned pack as
+    // one pitched 3-D copy (DMA): a box-copy kernel queued while other lanes' decode waves hold the
+    // CUs waited for their slots (trace: pack median 5 ms at 8 lanes, 20 ms at 2 lanes with bigger
+    // batches), and the copy engines need none.
+    for (size_t k = 0; k < B.calls.size(); k++) {
+      const BoxRuns &R = boxes[k];
+      if (!R.n_runs) continue;
+      const uint64_t w = R.run_bytes;
+      const uint64_t h = R.outer >= 1 ? R.shape[R.outer - 1] : 1, depth = R.outer >= 2 ? R.shape[0] : 1;
+      const uint64_t pitch = R.outer >= 1 ? R.stride[R.outer - 1] : w;
+      const uint64_t sy = R.outer >= 2 ? R.stride[0] / pitch : h;
+      hipMemcpy3DParms p3{};
+      p3.srcPtr = make_hipPitchedPtr(dout + R.base, pitch, w, sy);
+      p3.dstPtr = make_hipPitchedPtr(B.pack + B.calls[k]->pack_off, w, w, h);
+      p3.extent = make_hipExtent(w, h, depth);
+      p3.kind = hipMemcpyDeviceToHost;
+      HIPCHK(hipMemcpy3DAsync(&p3, s));
+    }
+  } else {
+    uint8_t *dpack = H.sc.dev<uint8_t>(pack_bytes ? pack_bytes : 1);
+    for (size_t k = 0; k < B.calls.size(); k++) {
+      const BoxRuns &R = boxes[k];
+      ZgBoxCopy P{};
+      P.outer = R.outer;
+      for (uint32_t d = 0; d < R.outer; d++) {
+        P.shape[d] = R.shape[d];
+        P.src_stride[d] = R.stride[d];
+      }
+      uint64_t cs = R.run_bytes;  // compact strides of the outer axes
+      for (int d = (int)R.outer - 1; d >= 0; d--) {
+        P.dst_stride[d] = cs;
+        cs *= R.shape[d];
+      }
+      P.src_base = R.base;
+      P.dst_base = B.calls[k]->pack_off;
+      P.run_bytes = R.run_bytes;
+      P.n_runs = R.n_runs;
+      HIPCHK(launch_box_copy(dout, dpack, P, s));
+    }
+    if (co_tracing()) {
+      HIPCHK(hipStreamSynchronize(s));
+      co_trace("packed", B.id, 1);
+    }
+    if (pack_bytes) HIPCHK(hipMemcpyAsync(B.pack, dpack, pack_bytes, hipMemcpyDeviceToHost, s));
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  co_trace("d2h-done", B.id, pack_bytes);
   for (size_t k = 0; k < B.calls.size(); k++) {
     CoCall &c = *B.calls[k];
     c.rc = 0;
@@ -3037,7 +1725,7 @@ static void co_run(CoBatch &B, Lane *LN) {
 // leader staging every caller's pageable bytes itself. Ranges (descriptors sorted by address, touching
 // ones merged) are placed back to back; local[i].enc points into the pinned copy. Returns nullptr
 // (local untouched) when there is nothing to copy or the bytes are pinned already.
-static uint8_t *pin_caller_inputs(zgpu_ctx *C, const zgpu_chunk_desc *descs, uint64_t n,
+static uint8_t *pin_caller_inputs(PoolBlocks &mem, const zgpu_chunk_desc *descs, uint64_t n,
                                   std::vector<zgpu_chunk_desc> &local) {
   std::vector<uint64_t> order;
   for (uint64_t i = 0; i < n; i++)
@@ -3070,7 +1758,7 @@ static uint8_t *pin_caller_inputs(zgpu_ctx *C, const zgpu_chunk_desc *descs, uin
   if (pinned) return nullptr;
   uint64_t cls = 4ull << 20;  // power-of-two classes: the pooled buffers are reused call after call
   while (cls < total) cls <<= 1;
-  uint8_t *pin = (uint8_t *)C->host_alloc(cls);
+  uint8_t *pin = mem.pinned<uint8_t>(cls);
   std::vector<uint8_t *> d;
   std::vector<const uint8_t *> sp;
   std::vector<uint64_t> ln;
@@ -3088,19 +1776,6 @@ static uint8_t *pin_caller_inputs(zgpu_ctx *C, const zgpu_chunk_desc *descs, uin
   return pin;
 }
 
-// zgpu_decode_pinned's result: a pooled pinned buffer of the context, or a slice of a coalesced
-// batch's pack (the batch, and with it the pack, lives until every caller released its result)
-struct zgpu_result {
-  zgpu_ctx *ctx = nullptr;
-  uint8_t *own = nullptr;             // pooled pinned buffer (uncoalesced call)
-  std::shared_ptr<CoBatch> batch;     // coalesced call: the batch holding the pack
-  ~zgpu_result() {
-    if (own) ctx->host_free(own);
-    batch.reset();
-    ctx_unref(ctx);
-  }
-};
-
 static int coalesced_call(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *descs, uint64_t n,
                           const zgpu_out_view &V, uint32_t flags, int32_t *status,
                           zgpu_result **keep = nullptr, const void **keep_data = nullptr) {
@@ -3111,13 +1786,10 @@ static int coalesced_call(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *de
     return !e || std::atoi(e) != 0;
   }();
   std::vector<zgpu_chunk_desc> pinned_descs;
-  struct PinGuard {
-    zgpu_ctx *C;
-    uint8_t *p;
-    ~PinGuard() { C->host_free(p); }
-  } pin{C, pin_in ? pin_caller_inputs(C, descs, n, pinned_descs) : nullptr};
-  co_trace("pinned", 0, pin.p ? 1 : 0);
-  if (pin.p) descs = pinned_descs.data();
+  PoolBlocks pin_mem(C);  // pinned host memory the batch's H2D reads: this call outlives its batch's run
+  const uint8_t *pin = pin_in ? pin_caller_inputs(pin_mem, descs, n, pinned_descs) : nullptr;
+  co_trace("pinned", 0, pin ? 1 : 0);
+  if (pin) descs = pinned_descs.data();
   CoCall me{ch, nd, descs, n, V, flags, status};
   for (uint64_t i = 0; i < n; i++)
     if (descs[i].enc) me.enc_bytes += descs[i].enc_len;
@@ -3247,7 +1919,7 @@ static int decode_entry(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *desc
   return rc;
 }
 
-static void delete_coalescer(Coalescer *co) { delete co; }
+void delete_coalescer(Coalescer *co) { delete co; }
 
 extern "C" {
 
@@ -3421,6 +2093,7 @@ int zgpu_decode_files(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *descs,
   const bool host_out = !(flags & ZGPU_OUT_DEVICE);
   for (hipStream_t &cs : LN->copy)
     if (!cs) HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+  Scratch sc(C, s);  // declared first: returned after cleanup() below drained the streams
   uint8_t *enc_dev = nullptr, *dout = (uint8_t *)out, *slab[2] = {nullptr, nullptr}, *pin_stage = nullptr;
   const uint64_t stage_slab = 64ull << 20;
   std::vector<hipEvent_t> ev(groups.size(), nullptr);
@@ -3431,19 +2104,14 @@ int zgpu_decode_files(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *descs,
     plans.clear();
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
-    C->dev_free(enc_dev);
-    if (host_out) C->dev_free(dout);
-    C->host_free(slab[0]);
-    C->host_free(slab[1]);
-    C->host_free(pin_stage);
   };
   int rc = 0;
   const bool fused = fused_plannable(*ch->chain) && uniform_shapes(descs, n, nd);
   std::vector<int32_t> all(n, 0);
   try {
-    enc_dev = (uint8_t *)C->dev_alloc(total ? total : 1);
+    enc_dev = sc.dev<uint8_t>(total ? total : 1);
     if (host_out) {
-      dout = (uint8_t *)C->dev_alloc(out_bytes ? out_bytes : 1);
+      dout = sc.dev<uint8_t>(out_bytes ? out_bytes : 1);
       uint64_t covered = 0;  // disjoint regions: equal volumes mean full coverage (no upload)
       for (uint64_t i = 0; i < n; i++) {
         uint64_t v = 1;
@@ -3451,11 +2119,11 @@ int zgpu_decode_files(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *descs,
         covered += v;
       }
       if (covered != out_elems) {
-        pin_stage = (uint8_t *)C->host_alloc(2 * stage_slab);
+        pin_stage = sc.pinned<uint8_t>(2 * stage_slab);
         HIPCHK(h2d_bytes(dout, (const uint8_t *)out, out_bytes, pin_stage, stage_slab, threads, s));
       }
     }
-    for (int k = 0; k < 2 && k < (int)groups.size(); k++) slab[k] = (uint8_t *)C->host_alloc(max_g);
+    for (int k = 0; k < 2 && k < (int)groups.size(); k++) slab[k] = sc.pinned<uint8_t>(max_g);
     for (hipEvent_t &e : ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     for (size_t g = 0; g < groups.size(); g++) {
       const Group &G = groups[g];
@@ -3499,7 +2167,7 @@ int zgpu_decode_files(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *descs,
       if (!rc) rc = all[i];
     }
     if (host_out) {
-      if (!pin_stage) pin_stage = (uint8_t *)C->host_alloc(2 * stage_slab);
+      if (!pin_stage) pin_stage = sc.pinned<uint8_t>(2 * stage_slab);
       HIPCHK(d2h_bytes((uint8_t *)out, dout, out_bytes, pin_stage, stage_slab, threads, s));
     }
   } catch (...) {
@@ -3510,685 +2178,6 @@ int zgpu_decode_files(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *descs,
   if (rc) set_err(rc, zgpu_status_name(rc));
   return rc;
   ABI_GUARD_END
-}
-
-// Encoded size of one chunk for a fixed-size chain (BytesRepresentation::FixedSize), -1 if variable.
-int64_t zgpu_chain_encoded_size(const zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape) {
-  if (!ch || !chunk_shape || nd == 0 || nd > ZGPU_MAX_DIMS) return -1;
-  uint64_t n = 1;
-  for (uint32_t d = 0; d < nd; d++) n *= chunk_shape[d];
-  return chain_fixed_encoded_size(*ch->chain, n);
-}
-
-// Upper bound of one chunk's encoded size: the fixed size, a compressing chain's bounded size
-// (chain_encoded_bound), or for sharding_indexed every inner chunk at its bound plus the index
-// (ShardingCodec::encoded_shard_bounded_size, sharding_codec.rs:924-945, BytesRepresentation::
-// BoundedSize); -1 if unbounded.
-int64_t zgpu_chain_encoded_bound(const zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape) {
-  if (!ch || !chunk_shape || nd == 0 || nd > ZGPU_MAX_DIMS) return -1;
-  const Chain &c = *ch->chain;
-  if (c.a2b.kind != CodecKind::Sharding) {
-    uint64_t n = 1;
-    for (uint32_t d = 0; d < nd; d++) n *= chunk_shape[d];
-    return chain_encoded_bound(c, n);
-  }
-  for (const Codec &k : c.a2a)
-    if (!is_value_codec(k.kind)) return -1;  // (value codecs keep the shape; encode strips them)
-  if (!c.b2b.empty() || c.a2b.inner_shape.size() != nd) return -1;
-  uint64_t n_inner = 1, inner_n = 1;
-  for (uint32_t d = 0; d < nd; d++) {
-    const uint64_t is = c.a2b.inner_shape[d];
-    if (chunk_shape[d] % is) return -1;
-    n_inner *= chunk_shape[d] / is;
-    inner_n *= is;
-  }
-  const int64_t E = chain_encoded_bound(*c.a2b.inner, inner_n);
-  const int64_t X = chain_fixed_encoded_size(*c.a2b.index, n_inner * 2);
-  if (E < 0 || X < 0) return -1;
-  return (int64_t)n_inner * E + X;
-}
-
-}  // extern "C"
-
-// CodecChain::encode (codec_chain.rs:528-555) of a fixed-size chain for n chunks of a device array
-// into device buffers h_dst[i] (chunk origins h_starts[i*nd..]): one gather (transposes + endianness +
-// innermost shuffle, fill past the array edge), then one k_crc32c_encode launch per crc32c codec.
-// Enqueues only (no synchronisation); d_tab: device table of n dst pointers + n*nd origins.
-// The gather's parameters: the chain's transposes, bytes endianness and (shuffle) an innermost
-// numcodecs.shuffle over the data type size, chunk data at data_off bytes into each destination.
-static ZgEncode encode_params(const Chain &c, uint32_t nd, const uint64_t *chunk_shape, const uint64_t *array_shape,
-                              bool shuffle, uint64_t data_off) {
-  ZgEncode P{};
-  P.nd = nd;
-  P.es = c.es;
-  P.comp = c.comp;
-  P.swap = (c.a2b.big_endian && c.comp > 1) ? 1 : 0;
-  P.shuffle = shuffle;
-  P.nelem = 1;
-  for (uint32_t d = 0; d < nd; d++) P.nelem *= chunk_shape[d];
-  P.data_off = data_off;
-  uint32_t m[ZG_MAXD];
-  composed_axes(c, nd, m);
-  uint64_t stride = 1;
-  for (int d = (int)nd - 1; d >= 0; d--) {
-    P.array_shape[d] = array_shape[d];
-    P.array_stride[d] = stride;
-    stride *= array_shape[d];
-  }
-  for (uint32_t a = 0; a < nd; a++) {
-    P.dec_axis[a] = m[a];
-    P.enc_shape[a] = chunk_shape[m[a]];
-  }
-  {
-    uint64_t es_ = 1;
-    for (int a = (int)nd - 1; a >= 0; a--) {
-      P.enc_stride_of_dec[m[a]] = es_;
-      es_ *= P.enc_shape[a];
-    }
-    for (uint32_t d = 0; d < nd; d++) P.dec_shape[d] = chunk_shape[d];
-    // tiled encode: the axis (other than the encoded and the array innermost) with the smallest
-    // encoded stride, so the TJ slabs of a block are adjacent encoded rows
-    P.tile_b = ZG_MAXD;
-    for (uint32_t d = 0; d + 1 < nd; d++) {
-      if (d == m[nd - 1]) continue;
-      if (P.tile_b == ZG_MAXD || P.enc_stride_of_dec[d] < P.enc_stride_of_dec[P.tile_b]) P.tile_b = d;
-    }
-  }
-  std::memcpy(P.fill, c.fill, sizeof(P.fill));
-  P.aligned = 0;
-  return P;
-}
-
-static int encode_fixed(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t *chunk_shape, const void *array,
-                        const uint64_t *array_shape, const std::vector<uint64_t> &h_tab, uint64_t n,
-                        std::vector<void *> &owned, hipStream_t s, ZgEncode *out_P = nullptr) {
-  if (c.a2b.kind != CodecKind::Bytes) return set_err(ZGPU_UNSUPPORTED, "encode: array->bytes codec must be bytes");
-  for (const Codec &k : c.a2a)
-    if (k.kind == CodecKind::Transpose && k.order.size() != nd) return set_err(ZGPU_INVALID_ARGUMENT, "transpose order rank != ndim");
-  bool shuffle = false;
-  int n_start = 0;
-  for (size_t i = 0; i < c.b2b.size(); i++) {
-    const Codec &k = c.b2b[i];
-    if (k.kind == CodecKind::Shuffle && i == 0 && k.elementsize == c.es) shuffle = true;
-    else if (is_checksum(k.kind)) n_start += k.at_start ? 1 : 0;
-    else return set_err(ZGPU_UNSUPPORTED, "encode: only transpose / bytes / numcodecs.shuffle (innermost, "
-                                          "elementsize = data type size) / crc32c / adler32 / fletcher32 / gzip run "
-                                          "on the GPU write path");
-  }
-  ZgEncode P = encode_params(c, nd, chunk_shape, array_shape, shuffle, 4ull * n_start);
-  bool aligned = (P.data_off % c.es) == 0;
-  for (uint64_t i = 0; i < n; i++)
-    if (h_tab[i] % 16) aligned = false;
-  P.aligned = aligned;
-  if (out_P) *out_P = P;
-  if (!n) return ZGPU_OK;
-  uint64_t *d = (uint64_t *)C->dev_alloc(h_tab.size() * 8);
-  owned.push_back(d);
-  HIPCHK(hipMemcpyAsync(d, h_tab.data(), h_tab.size() * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(launch_encode_gather(d, d + n, (const uint8_t *)array, P, (uint32_t)n, s));
-  uint64_t lo = P.data_off, len = P.nelem * c.es;
-  for (const Codec &k : c.b2b) {
-    if (!is_checksum(k.kind)) continue;
-    if (k.kind == CodecKind::Crc32c)
-      HIPCHK(launch_crc32c_encode(d, (uint32_t)n, lo, len, k.at_start ? 1 : 0, s));
-    else
-      HIPCHK(launch_linsum_encode(k.kind == CodecKind::Adler32 ? CK_ADLER32 : CK_FLETCHER32, d, (uint32_t)n, lo, len,
-                                  k.at_start ? 1 : 0, s));
-    if (k.at_start) lo -= 4;
-    len += 4;
-  }
-  return ZGPU_OK;
-}
-
-static bool chain_compresses(const Chain &c) {
-  for (const Codec &k : c.b2b)
-    if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib || k.kind == CodecKind::Zstd ||
-        k.kind == CodecKind::Blosc || k.kind == CodecKind::Bz2)
-      return true;
-  return false;  // (bz2 is refused by encode_var: it has no encoder on the GPU)
-}
-
-// CodecChain::encode (codec_chain.rs:528-555) of a chain with a compressor, for n chunks whose origins
-// are origins[i*nd..]: the gather (transposes, endianness, innermost shuffle) into 64 B-headroom
-// slots, then the bytes->bytes codecs in metadata order over the items {src, len}: crc32c appended /
-// prepended in place, gzip into the other slot pool (k_gzip_encode). Enqueues only; on return the
-// device item table and statuses describe every chunk's encoded bytes (inside scratch `owned`), and
-// *d_tab_out is the device table [n gather destinations | n*nd origins].
-static int encode_var(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t *chunk_shape, const void *array,
-                      const uint64_t *array_shape, const uint64_t *origins, uint64_t n, std::vector<void *> &owned,
-                      hipStream_t s, ZgItem **d_items_out, uint32_t **d_status_out, uint64_t **d_tab_out,
-                      ZgEncode *P_out) {
-  if (c.a2b.kind != CodecKind::Bytes) return set_err(ZGPU_UNSUPPORTED, "encode: array->bytes codec must be bytes");
-  for (const Codec &k : c.a2a)
-    if (k.kind == CodecKind::Transpose && k.order.size() != nd) return set_err(ZGPU_INVALID_ARGUMENT, "transpose order rank != ndim");
-  uint64_t nelem = 1;
-  for (uint32_t d = 0; d < nd; d++) nelem *= chunk_shape[d];
-  bool shuffle = false;
-  uint64_t size = nelem * c.es, max_size = size;
-  uint32_t n_crc = 0;
-  for (size_t i = 0; i < c.b2b.size(); i++) {
-    const Codec &k = c.b2b[i];
-    if (k.kind == CodecKind::Shuffle && i == 0 && k.elementsize == c.es) {
-      shuffle = true;
-    } else if (is_checksum(k.kind)) {
-      size += 4;
-      n_crc++;
-    } else if (k.kind == CodecKind::Gzip) {
-      size = gzip_bound(size);
-    } else if (k.kind == CodecKind::Zlib) {
-      size = zlib_bound(size);  // k_gzip_encode keeps to it (zlib_bounded)
-    } else if (k.kind == CodecKind::Zstd) {
-      size = zstd_bound(size);
-    } else if (k.kind == CodecKind::Blosc) {
-      size += 16;
-    } else if (k.kind == CodecKind::Bz2) {
-      return set_err(ZGPU_UNSUPPORTED, "encode: numcodecs.bz2 is decode-only on the GPU");
-    } else {
-      return set_err(ZGPU_UNSUPPORTED, "encode: only transpose / bytes / numcodecs.shuffle (innermost, elementsize = "
-                                       "data type size) / crc32c / adler32 / fletcher32 / gzip / zlib / zstd / blosc "
-                                       "run on the GPU write path");
-    }
-    max_size = std::max(max_size, size);
-  }
-  if (n_crc > 14) return set_err(ZGPU_UNSUPPORTED, "encode: too many checksum codecs");
-  constexpr uint64_t HR = 64;  // headroom in front of a slot's bytes (crc32c at the start)
-  const uint64_t pitch = (HR + max_size + 4 * n_crc + 16 + 255) & ~(uint64_t)255;
-  bool gz = false;  // a compressor: its output goes to the other slot pool
-  for (const Codec &k : c.b2b)
-    gz = gz || k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib || k.kind == CodecKind::Zstd ||
-         k.kind == CodecKind::Blosc;
-  uint8_t *pool[2] = {(uint8_t *)C->dev_alloc(std::max<uint64_t>(n * pitch, 1)), nullptr};
-  owned.push_back(pool[0]);
-  if (gz) {
-    pool[1] = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n * pitch, 1));
-    owned.push_back(pool[1]);
-  }
-  // gather into pool 0
-  std::vector<uint64_t> tab(n * (1 + nd));
-  for (uint64_t i = 0; i < n; i++) tab[i] = (uint64_t)(pool[0] + i * pitch + HR);
-  std::memcpy(tab.data() + n, origins, n * nd * 8);
-  uint64_t *d_tab = (uint64_t *)C->dev_alloc(std::max<size_t>(tab.size() * 8, 8));
-  owned.push_back(d_tab);
-  HIPCHK(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
-  ZgEncode P = encode_params(c, nd, chunk_shape, array_shape, shuffle, 0);
-  P.aligned = (c.es <= 16 && (HR % 16) == 0 && (pitch % 16) == 0) ? 1u : 0u;
-  if (n) HIPCHK(launch_encode_gather(d_tab, d_tab + n, (const uint8_t *)array, P, (uint32_t)n, s));
-  // items over the gathered chunks
-  std::vector<ZgItem> items(n);
-  for (uint64_t i = 0; i < n; i++) items[i] = ZgItem{tab[i], nelem * c.es, (uint32_t)i, 0, 0, 0};
-  ZgItem *d_items = (ZgItem *)C->dev_alloc(std::max<uint64_t>(n * sizeof(ZgItem), 1));
-  uint32_t *d_status = (uint32_t *)C->dev_alloc(std::max<uint64_t>(n * 4, 4));
-  owned.push_back(d_items);
-  owned.push_back(d_status);
-  HIPCHK(hipMemcpyAsync(d_items, items.data(), n * sizeof(ZgItem), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(d_status, 0, std::max<uint64_t>(n * 4, 4), s));
-  int cur = 0;
-  uint32_t *sym = nullptr;
-  uint8_t *zscr = nullptr;
-  uint64_t in_size = nelem * c.es;  // the current stage's input bound
-  bool var_len = false;             // an earlier stage made the lengths variable
-  for (size_t i = 0; i < c.b2b.size(); i++) {
-    const Codec &k = c.b2b[i];
-    const uint64_t stage_in = in_size;
-    if (k.kind == CodecKind::Blosc) {
-      // BloscCodec::encode (blosc_codec_via_blosc_src.rs:113-128): blosclz / lz4 / lz4hc / zlib / zstd
-      // streams on the GPU
-      const uint32_t comp = (k.cname == "lz4" || k.cname == "lz4hc") ? (uint32_t)BL_COMP_LZ4
-                            : k.cname == "zstd"                       ? (uint32_t)BL_COMP_ZSTD
-                            : k.cname == "blosclz"                    ? (uint32_t)BL_COMP_BLOSCLZ
-                            : k.cname == "zlib"                       ? (uint32_t)BL_COMP_ZLIB
-                            : k.cname == "snappy"                     ? (uint32_t)BL_COMP_SNAPPY
-                                                                      : UINT32_MAX;
-      if (comp == UINT32_MAX)
-        return set_err(ZGPU_UNSUPPORTED, "encode: blosc cname '" + k.cname +
-                                             "' (the GPU writes blosclz, lz4, lz4hc, snappy, zlib and zstd)");
-      if (var_len) return set_err(ZGPU_UNSUPPORTED, "encode: blosc after a variable-length codec");
-      const uint32_t ts = std::max<uint32_t>(1, k.elementsize);
-      const int sh = k.shuffle >= 0 ? k.shuffle : (k.elementsize > 0 ? 2 : 0);  // zarrs' default (:119-123)
-      const BloscEnc E = blosc_enc_params(comp, (uint32_t)sh, ts, stage_in, k.blocksize);
-      uint8_t *bscr = (uint8_t *)C->dev_alloc(blosc_encode_scratch(E, (uint32_t)n));
-      owned.push_back(bscr);
-      cur ^= 1;
-      HIPCHK(launch_blosc_encode(d_items, d_status, (uint32_t)n, E, pool[cur], pitch, bscr, k.level, s));
-      in_size += 16;
-      var_len = true;
-      continue;
-    }
-    if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib || k.kind == CodecKind::Zstd) var_len = true;
-    in_size = is_checksum(k.kind) ? in_size + 4 : k.kind == CodecKind::Gzip ? gzip_bound(in_size)
-              : k.kind == CodecKind::Zlib ? zlib_bound(in_size)
-              : k.kind == CodecKind::Zstd ? zstd_bound(in_size) : in_size;
-    if (k.kind == CodecKind::Crc32c) {
-      HIPCHK(launch_crc32c_items(d_items, d_status, (uint32_t)n, k.at_start ? 1 : 0, s));
-    } else if (k.kind == CodecKind::Adler32 || k.kind == CodecKind::Fletcher32) {
-      HIPCHK(launch_linsum_items(k.kind == CodecKind::Adler32 ? CK_ADLER32 : CK_FLETCHER32, d_items, d_status,
-                                 (uint32_t)n, k.at_start ? 1 : 0, s));
-    } else if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib) {
-      if (!sym) {
-        sym = (uint32_t *)C->dev_alloc((uint64_t)gzip_encode_grid((uint32_t)std::max<uint64_t>(n, 1)) * GZE_BLK_SYMS * 4);
-        owned.push_back(sym);
-      }
-      cur ^= 1;
-      HIPCHK(launch_gzip_encode(d_items, d_status, (uint32_t)n, pool[cur], pitch, sym, k.level, s,
-                                k.kind == CodecKind::Zlib, k.kind == CodecKind::Zlib));
-    } else if (k.kind == CodecKind::Zstd) {
-      zscr = (uint8_t *)C->dev_alloc(zstd_encode_scratch((uint32_t)n, stage_in));
-      owned.push_back(zscr);
-      cur ^= 1;
-      HIPCHK(launch_zstd_encode(d_items, d_status, (uint32_t)n, stage_in, pool[cur], pitch, zscr, k.checksum ? 1 : 0,
-                                s));
-    }
-  }
-  *d_items_out = d_items;
-  *d_status_out = d_status;
-  if (d_tab_out) *d_tab_out = d_tab;
-  if (P_out) *P_out = P;
-  return ZGPU_OK;
-}
-
-// first non-zero of n device statuses (read back synchronously), 0 if none
-static int first_status(const uint32_t *d_status, uint64_t n, hipStream_t s) {
-  std::vector<uint32_t> h(n);
-  if (n) HIPCHK(hipMemcpyAsync(h.data(), d_status, n * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  for (uint32_t v : h)
-    if (v) return (int)v;
-  return 0;
-}
-
-// a chain with a compressor, unsharded: encode_var, then every chunk copied to its destination
-static int encode_compressed(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t *chunk_shape, const void *array,
-                             const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint64_t *enc_lens,
-                             std::vector<void *> &owned, hipStream_t s) {
-  uint64_t nelem = 1;
-  for (uint32_t d = 0; d < nd; d++) nelem *= chunk_shape[d];
-  const int64_t bound = chain_encoded_bound(c, nelem);
-  if (bound < 0) return set_err(ZGPU_UNSUPPORTED, "encode: the chain's encoded size is not bounded");
-  for (uint64_t i = 0; i < n; i++)
-    if (!descs[i].dst || descs[i].dst_cap < (uint64_t)bound)
-      return set_err(ZGPU_INVALID_ARGUMENT, "encode: destination missing or smaller than the encoded bound");
-  std::vector<uint64_t> org(n * nd), dc(2 * n);
-  for (uint64_t i = 0; i < n; i++) {
-    for (uint32_t d = 0; d < nd; d++) org[i * nd + d] = descs[i].chunk_start[d];
-    dc[i] = (uint64_t)descs[i].dst;
-    dc[n + i] = descs[i].dst_cap;
-  }
-  ZgItem *items = nullptr;
-  uint32_t *st = nullptr;
-  int rc = encode_var(C, c, nd, chunk_shape, array, array_shape, org.data(), n, owned, s, &items, &st, nullptr, nullptr);
-  if (rc) return rc;
-  uint64_t *d_dc = (uint64_t *)C->dev_alloc(8 * (3 * n));
-  owned.push_back(d_dc);
-  HIPCHK(hipMemcpyAsync(d_dc, dc.data(), 16 * n, hipMemcpyHostToDevice, s));
-  HIPCHK(launch_encode_place(items, st, d_dc, d_dc + n, d_dc + 2 * n, (uint32_t)n, s));
-  std::vector<uint64_t> lens(n);
-  HIPCHK(hipMemcpyAsync(lens.data(), d_dc + 2 * n, 8 * n, hipMemcpyDeviceToHost, s));
-  rc = first_status(st, n, s);
-  if (rc) return set_err(rc, std::string("encode: ") + zgpu_status_name(rc));
-  if (enc_lens) std::memcpy(enc_lens, lens.data(), 8 * n);
-  return ZGPU_OK;
-}
-
-// sharding_indexed over a fixed-size inner chain (ShardingCodecBound::encode_bounded,
-// sharding_codec.rs:924-1085, SubchunkWriteOrder::C): all inner chunks of all shards encoded into
-// temporary slots in one batch, all-fill inner chunks omitted, the rest laid out in C order with the
-// encoded index at the start or the end; shard lengths to enc_lens.
-static int encode_sharded(zgpu_ctx *C, const Chain &top, uint32_t nd, const uint64_t *shard_shape, const void *array,
-                          const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint64_t *enc_lens,
-                          std::vector<void *> &owned, hipStream_t s) {
-  const Chain &inner = *top.a2b.inner, &xc = *top.a2b.index;
-  if (!top.a2a.empty() || !top.b2b.empty())
-    return set_err(ZGPU_UNSUPPORTED, "encode: codecs around sharding_indexed");
-  if (top.a2b.inner_shape.size() != nd) return set_err(ZGPU_INVALID_ARGUMENT, "sharding chunk_shape rank");
-  if (xc.a2b.kind != CodecKind::Bytes || !xc.a2a.empty())
-    return set_err(ZGPU_UNSUPPORTED, "index_codecs must be bytes (+crc32c)");
-  for (const Codec &k : xc.b2b)
-    if (k.kind != CodecKind::Crc32c) return set_err(ZGPU_UNSUPPORTED, "index_codecs must be bytes (+crc32c)");
-  uint64_t cps[ZG_MAXD], n_inner = 1, inner_n = 1;
-  for (uint32_t d = 0; d < nd; d++) {
-    const uint64_t is = top.a2b.inner_shape[d];
-    if (shard_shape[d] % is) return set_err(ZGPU_INVALID_ARGUMENT, "shard shape not a multiple of chunk_shape");
-    cps[d] = shard_shape[d] / is;
-    n_inner *= cps[d];
-    inner_n *= is;
-  }
-  const int64_t X = chain_fixed_encoded_size(xc, n_inner * 2);
-  if (chain_compresses(inner)) {
-    // inner chunks of variable length: encode_var over all inner chunks of all shards, then the
-    // variable-length layout (C write order, all-fill inner chunks omitted) and the index crc32c
-    const int64_t EB = chain_encoded_bound(inner, inner_n);
-    if (EB < 0) return set_err(ZGPU_UNSUPPORTED, "encode: the inner chain's encoded size is not bounded");
-    const uint64_t bound = n_inner * (uint64_t)EB + (uint64_t)X;
-    uint64_t cap = UINT64_MAX;
-    for (uint64_t i = 0; i < n; i++) {
-      if (!descs[i].dst || descs[i].dst_cap < bound)
-        return set_err(ZGPU_INVALID_ARGUMENT, "encode: destination missing or smaller than the shard's bounded size");
-      cap = std::min(cap, descs[i].dst_cap);
-    }
-    const uint64_t n_chunks = n * n_inner;
-    std::vector<uint64_t> org(n_chunks * nd);
-    for (uint64_t i = 0; i < n; i++)
-      for (uint64_t k = 0; k < n_inner; k++) {
-        uint64_t rem = k;
-        for (int d = (int)nd - 1; d >= 0; d--) {
-          org[(i * n_inner + k) * nd + d] = descs[i].chunk_start[d] + (rem % cps[d]) * top.a2b.inner_shape[d];
-          rem /= cps[d];
-        }
-      }
-    ZgItem *items = nullptr;
-    uint32_t *st = nullptr;
-    uint64_t *d_tab = nullptr;
-    ZgEncode IP{};
-    int rc = encode_var(C, inner, nd, top.a2b.inner_shape.data(), array, array_shape, org.data(), n_chunks, owned, s,
-                        &items, &st, &d_tab, &IP);
-    if (rc) return rc;
-    uint64_t *d_sh = (uint64_t *)C->dev_alloc(8 * (3 * n + n_chunks));
-    uint32_t *d_nf = (uint32_t *)C->dev_alloc(4 * std::max<uint64_t>(n_chunks, 1) + 4 * n);
-    owned.push_back(d_sh);
-    owned.push_back(d_nf);
-    std::vector<uint64_t> hd(n);
-    for (uint64_t i = 0; i < n; i++) hd[i] = (uint64_t)descs[i].dst;
-    HIPCHK(hipMemcpyAsync(d_sh, hd.data(), 8 * n, hipMemcpyHostToDevice, s));
-    uint64_t *d_index_ptr = d_sh + n, *d_len = d_sh + 2 * n, *d_off = d_sh + 3 * n;
-    uint32_t *d_shst = d_nf + n_chunks;
-    int n_pre = 0;
-    for (const Codec &k : xc.b2b) n_pre += k.at_start ? 1 : 0;
-    ZgShardLayoutArgs A{n_inner, 0, cap, (uint64_t)X, 4ull * n_pre, top.a2b.at_start ? 1u : 0u,
-                        xc.a2b.big_endian ? 1u : 0u};
-    HIPCHK(launch_shard_encode_var(d_tab + n_chunks, (const uint8_t *)array, IP, (uint32_t)n_chunks, d_nf, items, st, A,
-                                   d_sh, d_off, d_index_ptr, d_len, d_shst, (uint32_t)n, s));
-    uint64_t lo = 4ull * n_pre, len = n_inner * 16;
-    for (const Codec &k : xc.b2b) {
-      HIPCHK(launch_crc32c_encode(d_index_ptr, (uint32_t)n, lo, len, k.at_start ? 1 : 0, s));
-      if (k.at_start) lo -= 4;
-      len += 4;
-    }
-    HIPCHK(hipMemcpyAsync(enc_lens, d_len, 8 * n, hipMemcpyDeviceToHost, s));
-    rc = first_status(st, n_chunks, s);
-    if (!rc) rc = first_status(d_shst, n, s);
-    if (rc) return set_err(rc == 1 ? ZGPU_HIP_ERROR : rc, std::string("encode: ") + zgpu_status_name(rc));
-    return ZGPU_OK;
-  }
-  const int64_t E = chain_fixed_encoded_size(inner, inner_n);
-  if (E < 0) return set_err(ZGPU_UNSUPPORTED, "encode: the inner chain of sharding_indexed must be fixed-size or "
-                                              "compressed by gzip");
-  const uint64_t bound = n_inner * (uint64_t)E + (uint64_t)X;
-  for (uint64_t i = 0; i < n; i++)
-    if (!descs[i].dst || descs[i].dst_cap < bound)
-      return set_err(ZGPU_INVALID_ARGUMENT, "encode: destination missing or smaller than the shard's bounded size");
-  const uint64_t pitch = ((uint64_t)E + 255) & ~(uint64_t)255, n_chunks = n * n_inner;
-  uint8_t *tmp = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n_chunks * pitch, 1));
-  owned.push_back(tmp);
-  // inner chunk k of shard i: dst slot, origin in the array
-  std::vector<uint64_t> tab(n_chunks * (1 + nd));
-  for (uint64_t i = 0; i < n; i++)
-    for (uint64_t k = 0; k < n_inner; k++) {
-      const uint64_t g = i * n_inner + k;
-      tab[g] = (uint64_t)(tmp + g * pitch);
-      uint64_t rem = k;
-      for (int d = (int)nd - 1; d >= 0; d--) {
-        tab[n_chunks + g * nd + d] = descs[i].chunk_start[d] + (rem % cps[d]) * top.a2b.inner_shape[d];
-        rem /= cps[d];
-      }
-    }
-  ZgEncode IP{};
-  int rc = encode_fixed(C, inner, nd, top.a2b.inner_shape.data(), array, array_shape, tab, n_chunks, owned, s, &IP);
-  if (rc) return rc;
-  const uint64_t *d_tab = (const uint64_t *)owned.back();  // [dst slots | origins] on the device
-  // per-shard tables: dst pointers, inner offsets, index positions, lengths; fill flags
-  uint64_t *d_sh = (uint64_t *)C->dev_alloc(8 * (3 * n + n_chunks));
-  uint32_t *d_nf = (uint32_t *)C->dev_alloc(4 * std::max<uint64_t>(n_chunks, 1));
-  owned.push_back(d_sh);
-  owned.push_back(d_nf);
-  std::vector<uint64_t> hd(n);
-  for (uint64_t i = 0; i < n; i++) hd[i] = (uint64_t)descs[i].dst;
-  HIPCHK(hipMemcpyAsync(d_sh, hd.data(), 8 * n, hipMemcpyHostToDevice, s));
-  uint64_t *d_index_ptr = d_sh + n, *d_len = d_sh + 2 * n, *d_off = d_sh + 3 * n;
-  int n_pre = 0;
-  for (const Codec &k : xc.b2b) n_pre += k.at_start ? 1 : 0;
-  ZgShardLayoutArgs A{n_inner, (uint64_t)E, pitch, (uint64_t)X, 4ull * n_pre, top.a2b.at_start ? 1u : 0u,
-                      xc.a2b.big_endian ? 1u : 0u};
-  HIPCHK(launch_shard_encode(d_tab + n_chunks, (const uint8_t *)array, IP, (uint32_t)n_chunks, d_nf, tmp, A, d_sh, d_off,
-                             d_index_ptr, d_len, (uint32_t)n, s));
-  uint64_t lo = 4ull * n_pre, len = n_inner * 16;
-  for (const Codec &k : xc.b2b) {
-    HIPCHK(launch_crc32c_encode(d_index_ptr, (uint32_t)n, lo, len, k.at_start ? 1 : 0, s));
-    if (k.at_start) lo -= 4;
-    len += 4;
-  }
-  HIPCHK(hipMemcpyAsync(enc_lens, d_len, 8 * n, hipMemcpyDeviceToHost, s));
-  return ZGPU_OK;
-}
-
-// packbits as the array->bytes codec (unsharded): the chunks are gathered (and transposed) as native
-// elements into temporary slots, k_packbits packs each slot, and the packed chunks, a 1-D uint8 array
-// of one slot per chunk, go through [bytes(uint8), bytes->bytes codecs...] to their destinations
-// (straight into them without bytes->bytes codecs).
-static int encode_packbits(zgpu_ctx *C, const Chain &c, uint32_t nd, const uint64_t *chunk_shape, const void *array,
-                           const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint64_t *enc_lens,
-                           std::vector<void *> &owned, hipStream_t s) {
-  const Codec &pb = c.a2b;
-  const uint32_t es = c.enc_es;
-  const uint64_t nelem = volume(chunk_shape, nd), packed = packbits_size(pb, nelem);
-  const uint64_t upitch = (nelem * es + 15) & ~(uint64_t)15, ppitch = (packed + 15) & ~(uint64_t)15;
-  Chain native = c;  // [array->array codecs..., bytes(native)]
-  native.b2b.clear();
-  native.a2b = Codec{};
-  native.a2b.kind = CodecKind::Bytes;
-  native.a2b.name = "bytes";
-  Chain packed_chain;  // [bytes(uint8), bytes->bytes codecs...]
-  packed_chain.es = packed_chain.comp = packed_chain.enc_es = packed_chain.enc_comp = 1;
-  packed_chain.data_type = packed_chain.enc_data_type = "uint8";
-  packed_chain.a2b = native.a2b;
-  packed_chain.b2b = c.b2b;
-  const bool direct = c.b2b.empty();
-  const int64_t bound = direct ? (int64_t)packed : chain_encoded_bound(packed_chain, packed);
-  if (bound < 0) return set_err(ZGPU_UNSUPPORTED, "encode: the chain's encoded size is not bounded");
-  for (uint64_t i = 0; i < n; i++)
-    if (!descs[i].dst || descs[i].dst_cap < (uint64_t)bound)
-      return set_err(ZGPU_INVALID_ARGUMENT, "encode: destination missing or smaller than the encoded bound");
-  uint8_t *U = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n * upitch, 1));
-  owned.push_back(U);
-  uint8_t *Pk = nullptr;
-  if (!direct) {
-    Pk = (uint8_t *)C->dev_alloc(std::max<uint64_t>(n * ppitch, 1));
-    owned.push_back(Pk);
-  }
-  std::vector<uint64_t> tab(n * (1 + nd)), ptab(2 * n);
-  for (uint64_t i = 0; i < n; i++) {
-    tab[i] = ptab[i] = (uint64_t)(U + i * upitch);
-    for (uint32_t d = 0; d < nd; d++) tab[n + i * nd + d] = descs[i].chunk_start[d];
-    ptab[n + i] = direct ? (uint64_t)descs[i].dst : (uint64_t)(Pk + i * ppitch);
-  }
-  int rc = encode_fixed(C, native, nd, chunk_shape, array, array_shape, tab, n, owned, s);
-  if (rc) return rc;
-  uint64_t *d_ptab = (uint64_t *)C->dev_alloc(ptab.size() * 8);
-  owned.push_back(d_ptab);
-  HIPCHK(hipMemcpyAsync(d_ptab, ptab.data(), ptab.size() * 8, hipMemcpyHostToDevice, s));
-  ZgPackBits P{};
-  P.nelem = nelem;
-  P.packed_len = packed;
-  P.ncomp = pb.pb_ncomp;
-  P.comp_bytes = es / pb.pb_ncomp;
-  P.first = pb.pb_first;
-  P.ext = pb.pb_last - pb.pb_first + 1;
-  P.sign = pb.pb_signed ? 1 : 0;
-  P.padding = (uint32_t)pb.pb_padding;
-  HIPCHK(launch_packbits(d_ptab, (uint32_t)n, P, s));
-  if (direct) {
-    HIPCHK(hipStreamSynchronize(s));  // ptab is read by the copy above
-    for (uint64_t i = 0; i < n; i++) enc_lens[i] = packed;
-    return ZGPU_OK;
-  }
-  // the packed chunks as chunk i = [i * ppitch, i * ppitch + packed) of a 1-D uint8 array
-  const uint64_t p_shape[1] = {n * ppitch}, p_chunk[1] = {packed};
-  std::vector<zgpu_encode_desc> pd(descs, descs + n);
-  for (uint64_t i = 0; i < n; i++) pd[i].chunk_start[0] = i * ppitch;
-  if (chain_compresses(packed_chain))
-    return encode_compressed(C, packed_chain, 1, p_chunk, Pk, p_shape, pd.data(), n, enc_lens, owned, s);
-  std::vector<uint64_t> t2(2 * n);
-  for (uint64_t i = 0; i < n; i++) {
-    t2[i] = (uint64_t)descs[i].dst;
-    t2[n + i] = i * ppitch;
-  }
-  rc = encode_fixed(C, packed_chain, 1, p_chunk, Pk, p_shape, t2, n, owned, s);
-  HIPCHK(hipStreamSynchronize(s));  // the tables are read by encode_fixed's copies
-  for (uint64_t i = 0; i < n; i++) enc_lens[i] = (uint64_t)bound;
-  return rc;
-}
-
-extern "C" {
-
-int zgpu_encode_chunks(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, const void *array,
-                       const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint32_t flags,
-                       uint64_t *enc_lens, void *stream) {
-  ABI_GUARD_BEGIN
-  if (!ch || !chunk_shape || !array || !array_shape || (n && !descs))
-    return set_err(ZGPU_INVALID_ARGUMENT, "NULL argument");
-  if (nd == 0 || nd > ZGPU_MAX_DIMS) return set_err(ZGPU_INVALID_ARGUMENT, "ndim out of range");
-  if ((flags & (ZGPU_ENC_DEVICE | ZGPU_OUT_DEVICE)) != (ZGPU_ENC_DEVICE | ZGPU_OUT_DEVICE))
-    return set_err(ZGPU_INVALID_ARGUMENT, "encode: array and destinations must be device memory");
-  for (uint64_t i = 0; i < n; i++)
-    for (uint32_t d = 0; d < nd; d++)
-      if (descs[i].chunk_start[d] >= array_shape[d])
-        return set_err(ZGPU_INVALID_ARGUMENT, "encode: chunk origin outside the array");
-  zgpu_ctx *C = ch->ctx;
-  HIPCHK(hipSetDevice(C->device));
-  LaneScope ls(C);
-  hipStream_t s = pick_stream(ls.L, stream);
-  if (!n) return ZGPU_OK;
-  std::vector<void *> owned;
-  int rc = 0;
-  try {
-    // value codecs (numcodecs.fixedscaleoffset, bitround) work element by element, so they commute with
-    // chunking and sharding: the caller's array is converted once into a device array of the innermost
-    // encoded type, which the chain without them, retyped, encodes (strip_value_codecs)
-    std::shared_ptr<Chain> stripped;
-    if (chain_has_value_codec(*ch->chain)) {
-      std::vector<Codec> steps;
-      stripped = strip_value_codecs(*ch->chain, steps);
-      retype_stripped(*stripped, *ch->chain);
-      array = value_encode_elements(C, steps, (const uint8_t *)array, volume(array_shape, nd), owned, s);
-    }
-    const Chain &c = stripped ? *stripped : *ch->chain;
-    if (c.a2b.kind == CodecKind::PackBits) {
-      uint64_t *hl = (uint64_t *)C->host_alloc(8 * n);
-      rc = encode_packbits(C, c, nd, chunk_shape, array, array_shape, descs, n, hl, owned, s);
-      HIPCHK(hipStreamSynchronize(s));
-      if (!rc && enc_lens) std::memcpy(enc_lens, hl, 8 * n);
-      C->host_free(hl);
-    } else if (c.a2b.kind == CodecKind::Sharding) {
-      uint64_t *hl = (uint64_t *)C->host_alloc(8 * n);
-      rc = encode_sharded(C, c, nd, chunk_shape, array, array_shape, descs, n, hl, owned, s);
-      HIPCHK(hipStreamSynchronize(s));
-      if (!rc && enc_lens) std::memcpy(enc_lens, hl, 8 * n);
-      C->host_free(hl);
-    } else if (chain_compresses(c)) {
-      uint64_t *hl = (uint64_t *)C->host_alloc(8 * n);
-      rc = encode_compressed(C, c, nd, chunk_shape, array, array_shape, descs, n, hl, owned, s);
-      HIPCHK(hipStreamSynchronize(s));
-      if (!rc && enc_lens) std::memcpy(enc_lens, hl, 8 * n);
-      C->host_free(hl);
-    } else {
-      const int64_t enc_size = chain_fixed_encoded_size(c, [&] {
-        uint64_t e = 1;
-        for (uint32_t d = 0; d < nd; d++) e *= chunk_shape[d];
-        return e;
-      }());
-      if (enc_size < 0 && c.a2b.kind == CodecKind::Bytes)
-        rc = set_err(ZGPU_UNSUPPORTED, "encode: only transpose / bytes / numcodecs.shuffle (innermost, elementsize = "
-                                       "data type size) / crc32c, or sharding_indexed over such a chain, run on "
-                                       "the GPU write path");
-      for (uint64_t i = 0; i < n && !rc; i++)
-        if (!descs[i].dst || descs[i].dst_cap < (uint64_t)std::max<int64_t>(enc_size, 0))
-          rc = set_err(ZGPU_INVALID_ARGUMENT, "encode: destination missing or smaller than the encoded size");
-      if (!rc) {
-        std::vector<uint64_t> tab(n * (1 + nd));
-        for (uint64_t i = 0; i < n; i++) {
-          tab[i] = (uint64_t)descs[i].dst;
-          for (uint32_t d = 0; d < nd; d++) tab[n + i * nd + d] = descs[i].chunk_start[d];
-        }
-        rc = encode_fixed(C, c, nd, chunk_shape, array, array_shape, tab, n, owned, s);
-        HIPCHK(hipStreamSynchronize(s));
-        if (!rc && enc_lens)
-          for (uint64_t i = 0; i < n; i++) enc_lens[i] = (uint64_t)enc_size;
-      }
-    }
-  } catch (...) {
-    (void)hipStreamSynchronize(s);
-    for (void *p : owned) C->dev_free(p);
-    throw;
-  }
-  for (void *p : owned) C->dev_free(p);
-  return rc;
-  ABI_GUARD_END
-}
-
-// One chunk (or shard) from host bytes, encoded on the GPU, the encoded bytes left in pooled pinned
-// memory for the caller to copy (the plugin's CodecChain::encode / ShardingCodecBound::encode).
-int zgpu_encode_pinned(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, const void *decoded,
-                       const void **enc, uint64_t *enc_len, zgpu_result **result) {
-  ABI_GUARD_BEGIN
-  if (enc) *enc = nullptr;
-  if (result) *result = nullptr;
-  if (!ch || !chunk_shape || !decoded || !enc || !enc_len || !result)
-    return set_err(ZGPU_INVALID_ARGUMENT, "NULL argument");
-  if (nd == 0 || nd > ZGPU_MAX_DIMS) return set_err(ZGPU_INVALID_ARGUMENT, "ndim out of range");
-  zgpu_ctx *C = ch->ctx;
-  HIPCHK(hipSetDevice(C->device));
-  const int64_t bound = zgpu_chain_encoded_bound(ch, nd, chunk_shape);
-  if (bound < 0) return set_err(ZGPU_UNSUPPORTED, "encode: the chain's encoded size is not bounded");
-  const uint64_t nbytes = volume(chunk_shape, nd) * ch->chain->es;
-  uint8_t *d_in = (uint8_t *)C->dev_alloc(nbytes ? nbytes : 1);
-  uint8_t *d_out = (uint8_t *)C->dev_alloc(bound ? (uint64_t)bound : 1);
-  std::unique_ptr<zgpu_result> R(new zgpu_result());
-  ctx_ref(C);
-  R->ctx = C;
-  int rc = 0;
-  try {
-    hipStream_t s;
-    {
-      LaneScope ls(C);
-      s = pick_stream(ls.L, nullptr);
-      HIPCHK(hipMemcpyAsync(d_in, decoded, nbytes, hipMemcpyHostToDevice, s));
-      HIPCHK(hipStreamSynchronize(s));
-    }
-    zgpu_encode_desc D{};
-    D.dst = d_out;
-    D.dst_cap = (uint64_t)bound;
-    uint64_t len = 0;
-    rc = zgpu_encode_chunks(ch, nd, chunk_shape, d_in, chunk_shape, &D, 1, ZGPU_ENC_DEVICE | ZGPU_OUT_DEVICE, &len,
-                            nullptr);
-    if (!rc) {
-      R->own = (uint8_t *)C->host_alloc(len ? len : 1);
-      LaneScope ls(C);
-      s = pick_stream(ls.L, nullptr);
-      HIPCHK(hipMemcpyAsync(R->own, d_out, len, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      *enc = R->own;
-      *enc_len = len;
-    }
-  } catch (...) {
-    C->dev_free(d_in);
-    C->dev_free(d_out);
-    throw;
-  }
-  C->dev_free(d_in);
-  C->dev_free(d_out);
-  if (rc) return rc;
-  *result = R.release();
-  return ZGPU_OK;
-  ABI_GUARD_END
-}
-
-int zgpu_encode_batch(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, const void *array,
-                      const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint32_t flags,
-                      void *hip_stream) {
-  if (ch && ch->chain->a2b.kind == CodecKind::Sharding)
-    return set_err(ZGPU_INVALID_ARGUMENT, "encode: sharding_indexed chunks have variable lengths: zgpu_encode_chunks");
-  if (ch && chain_compresses(*ch->chain))
-    return set_err(ZGPU_INVALID_ARGUMENT, "encode: compressed chunks have variable lengths: zgpu_encode_chunks");
-  return zgpu_encode_chunks(ch, nd, chunk_shape, array, array_shape, descs, n, flags, nullptr, hip_stream);
 }
 
 int zgpu_retrieve_array_subset_files(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape,
