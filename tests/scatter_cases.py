@@ -86,7 +86,7 @@ def composed_axes(orders, nd: int) -> list:
 
 
 def model_path(case) -> int:
-    """The kernel the plan builder picks for the chain (zgpu.cpp, the scatter-mode choice), restated."""
+    """The kernel the plan builder picks for the chain (plan_layout.cpp, scatter_mode), restated."""
     nd = len(case.chunk)
     if composed_axes(case.orders, nd)[-1] == nd - 1:
         return ROWS

@@ -8,6 +8,7 @@
 //   Shard[n_shards]    sharded descriptors: encoded shard {ptr,len}; index decoded into
 //   index[n_shards][n_inner*2] u64 (offset, nbytes) per inner chunk, C order of inner coords
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #define ZG_MAXD 8
@@ -64,6 +65,46 @@ struct GzDirect {
   uint32_t nd;           // <= 3 (axis 1 of a 3-d chunk has a power-of-two extent); byte strides < 4 GiB
   uint32_t lbs;          // log2 of the row bytes (chunk_shape[nd-1] * es, >= 16)
 };
+
+// What the host layout of a plan (plan_layout.hpp) shares with the launchers (kernels/launch.hpp), free
+// of HIP: the scatter modes, the shard index spec, the persistent tiled scatter's constants. The three
+// functions are defined in kernels/scatter.hip, next to the tile constants they share with the kernels.
+namespace zgpu {
+
+enum ScatterMode : uint32_t { SCATTER_ROWS = 0, SCATTER_TILED = 1, SCATTER_GENERIC = 2 };
+uint64_t scatter_units_per_item(uint32_t mode, const ZgScatter &P, const uint64_t *max_sel_shape);
+
+// Tiled scatter of uniform whole-chunk batches (k_scatter_tiled_p): per-plan constants of a batch
+// whose every item is a whole chunk of full TILE x TILE tiles on 16-B aligned rows. Strides in
+// elements; every offset inside a chunk and inside an item's output box fits 32 bits
+// (tiled_persistent_params checks all of it).
+struct ZgTiledP {
+  uint32_t upi;                 // units per item (= scatter_units_per_item)
+  uint32_t nta, ntl, nbg;       // tiles along A and Lx, slab groups along B
+  uint32_t bext;                // extent of B (1: no B axis)
+  uint32_t sL, sB, dA, dB;      // encoded stride of Lx and B, output stride of A and B
+  uint32_t nrest;               // the other axes, innermost first: extent, encoded and output stride
+  uint32_t rext[ZG_MAXD], rs[ZG_MAXD], rd[ZG_MAXD];
+};
+// false: the batch is not eligible (it keeps the one-unit-per-block kernel). geom: per item sel_start |
+// sel_shape | out_start (3 * nd); origin[i] receives the output element offset of item i's origin.
+bool tiled_persistent_params(const ZgScatter &P, const uint64_t *geom, size_t n_items, ZgTiledP &Q,
+                             uint64_t *origin);
+// whether n_items x upi units fit launch_scatter_tiled_p
+bool tiled_persistent_fits(uint64_t n_items, uint64_t upi);
+
+// Shard index: how launch_shard_index decodes every shard's index (bytes{endian} + optional crc32c chain).
+struct ZgIndexSpec {
+  uint64_t n_inner;      // inner chunks per shard
+  uint64_t index_bytes;  // encoded index size (incl. checksums)
+  uint32_t at_start;     // sharding index_location
+  uint32_t big_endian;   // index bytes codec endianness
+  uint32_t n_crc;        // number of crc32c codecs in the index chain (<= 4)
+  uint32_t crc_at_start[4];
+  uint32_t verify;       // validate_checksums
+};
+
+}  // namespace zgpu
 
 // device status codes (== zgpu.h)
 #define ZG_OK 0u

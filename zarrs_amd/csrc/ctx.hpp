@@ -31,6 +31,7 @@ struct SizeDetail {
 // thread_local in zgpu.cpp, its one definition; the other translation units reach it through these.
 int set_err(int st, const std::string &m);  // sets the thread's error message; returns st
 SizeDetail &size_detail();
+uint64_t *call_counters();  // CTR_N counters, summed over the plans the call ran
 struct HipFail {
   hipError_t e;
   const char *what;

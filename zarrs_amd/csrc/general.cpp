@@ -116,20 +116,12 @@ static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &ite
   for (uint32_t i = 0; i < items.size(); i++)
     if (!ist[i]) todo.push_back(i);
   if (todo.empty()) return;
-  Stage st{};
-  uint32_t hint_kind = UINT32_MAX;
-  switch (k.kind) {
-    case CodecKind::Crc32c:
-    case CodecKind::Adler32:
-    case CodecKind::Fletcher32: st.kind = checksum_stage(k.kind); st.at_start = k.at_start; break;
-    case CodecKind::Gzip: st.kind = ST_GZIP; hint_kind = SIZE_HINT_GZIP; break;
-    case CodecKind::Zlib: st.kind = ST_ZLIB; break;  // no size in the stream: the regrow loop below finds it
-    case CodecKind::Bz2: st.kind = ST_BZ2; break;    // likewise
-    case CodecKind::Zstd: st.kind = ST_ZSTD; hint_kind = SIZE_HINT_ZSTD; break;
-    case CodecKind::Blosc: st.kind = ST_BLOSC; hint_kind = SIZE_HINT_BLOSC; break;
-    case CodecKind::Shuffle: st.kind = ST_UNSHUFFLE; st.elementsize = k.elementsize; break;
-    default: throw ChainError{ZGPU_UNSUPPORTED, "codec '" + k.name + "' after sharding_indexed"};
-  }
+  const std::optional<Stage> known = stage_for(k);
+  if (!known) throw ChainError{ZGPU_UNSUPPORTED, "codec '" + k.name + "' after sharding_indexed"};
+  const Stage st = *known;
+  // the streams that carry their decoded size (a zlib or bz2 stream has none: the regrow loop below finds it)
+  const uint32_t hint_kind = st.kind == ST_GZIP ? SIZE_HINT_GZIP : st.kind == ST_ZSTD ? SIZE_HINT_ZSTD
+                             : st.kind == ST_BLOSC ? SIZE_HINT_BLOSC : UINT32_MAX;
   uint64_t cap = 0;
   if (st.kind == ST_UNSHUFFLE) {
     for (uint32_t t : todo) cap = std::max(cap, items[t].len);
@@ -153,23 +145,14 @@ static void shard_stage(GeneralCall &G, const Codec &k, std::vector<ZgItem> &ite
   cap = std::max<uint64_t>(cap, 256);
   // one stages-only plan over `set` with slots of `c` bytes; statuses in s, decoded items in res
   auto run = [&](const std::vector<uint32_t> &set, uint64_t c, std::vector<int32_t> &s, std::vector<ZgItem> &res) {
-    auto P = std::make_unique<zgpu_plan>(G.C);
+    std::vector<ZgItem> sub;
+    for (uint32_t t : set) sub.push_back(items[t]);
+    auto P = std::make_unique<zgpu_plan>(G.C, stages_only_layout(std::move(sub), st, c));
     P->validate = G.validate;
     P->nd = 1;
     P->n_desc = set.size();
     P->flags = G.flags;
     P->out_shape = {1};
-    P->item_desc_status.assign(set.size(), 0);
-    for (size_t j = 0; j < set.size(); j++) {
-      ZgItem it = items[set[j]];
-      it.desc = (uint32_t)j;
-      P->items.push_back(it);
-    }
-    st.pool = 0;
-    P->stages = {st};
-    P->n_pools = strips_only(st.kind) ? 0 : 1;
-    P->slot_bytes = (c + 255) & ~(uint64_t)255;
-    P->no_scatter = true;
     plan_upload(*P, G.s);
     plan_enqueue(*P, nullptr, G.s);
     s.assign(set.size(), 0);

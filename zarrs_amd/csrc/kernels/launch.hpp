@@ -34,7 +34,6 @@ inline uint32_t device_cu_count() {
   return cache[dev];
 }
 
-enum ScatterMode : uint32_t { SCATTER_ROWS = 0, SCATTER_TILED = 1, SCATTER_GENERIC = 2 };
 // slabs (TILE x TILE tiles at consecutive values of ZgScatter::tile_b) per tiled-scatter block
 constexpr __host__ __device__ int tiled_slabs(uint32_t es) { return es == 8 ? 2 : 4; }
 
@@ -42,32 +41,13 @@ hipError_t launch_scatter(const ZgItem *items, const uint64_t *geom, uint32_t *s
                           uint8_t *out, uint32_t n_items, uint32_t mode, uint64_t units_per_item,
                           hipStream_t s, uint32_t *live_scratch = nullptr);  // (n_items + 1) u32: rows mode
                                                                             // over the items not yet written
-uint64_t scatter_units_per_item(uint32_t mode, const ZgScatter &P, const uint64_t *max_sel_shape);
 
-// Tiled scatter of uniform whole-chunk batches (k_scatter_tiled_p): per-plan constants of a batch
-// whose every item is a whole chunk of full TILE x TILE tiles on 16-B aligned rows. Strides in
-// elements; every offset inside a chunk and inside an item's output box fits 32 bits
-// (tiled_persistent_params checks all of it).
-struct ZgTiledP {
-  uint32_t upi;                 // units per item (= scatter_units_per_item)
-  uint32_t nta, ntl, nbg;       // tiles along A and Lx, slab groups along B
-  uint32_t bext;                // extent of B (1: no B axis)
-  uint32_t sL, sB, dA, dB;      // encoded stride of Lx and B, output stride of A and B
-  uint32_t nrest;               // the other axes, innermost first: extent, encoded and output stride
-  uint32_t rext[ZG_MAXD], rs[ZG_MAXD], rd[ZG_MAXD];
-};
-// false: the batch is not eligible (it keeps the one-unit-per-block kernel). geom: per item sel_start |
-// sel_shape | out_start (3 * nd); origin[i] receives the output element offset of item i's origin.
-bool tiled_persistent_params(const ZgScatter &P, const uint64_t *geom, size_t n_items, ZgTiledP &Q,
-                             uint64_t *origin);
 // grid_cap: 0 (one workgroup per unit, as far as one launch goes), or the most workgroups to launch,
 // which then loop over the units (ZGPU_TILED_GRID: tests make a few loop over many). Returns
 // hipErrorInvalidConfiguration when the unit count does not fit the kernel's 32-bit unit index.
 hipError_t launch_scatter_tiled_p(const ZgItem *items, const uint64_t *geom, uint32_t *status, const uint64_t *origin,
                                   const ZgScatter &P, const ZgTiledP &Q, uint8_t *out, uint32_t n_items,
                                   uint32_t grid_cap, hipStream_t s);
-// whether n_items x upi units fit launch_scatter_tiled_p
-bool tiled_persistent_fits(uint64_t n_items, uint64_t upi);
 
 // Box copy between device arrays: run r (C order over the `outer` axes of `shape`) is run_bytes
 // contiguous bytes at src_base + sum(c_d * src_stride[d]) -> dst_base + sum(c_d * dst_stride[d]).
@@ -94,15 +74,6 @@ hipError_t launch_linsum_strip(uint32_t kind, ZgItem *items, uint32_t *status, u
 
 // Shard index: decode every shard's index (bytes{endian} + optional crc32c chain), then resolve
 // each sharded item's {src,len} or fill flag.  index_crc: 0 none, 1 end, 2 start.
-struct ZgIndexSpec {
-  uint64_t n_inner;      // inner chunks per shard
-  uint64_t index_bytes;  // encoded index size (incl. checksums)
-  uint32_t at_start;     // sharding index_location
-  uint32_t big_endian;   // index bytes codec endianness
-  uint32_t n_crc;        // number of crc32c codecs in the index chain (<= 4)
-  uint32_t crc_at_start[4];
-  uint32_t verify;       // validate_checksums
-};
 // keep_err: shards whose status is already non-zero keep it and are skipped (nested sharding's
 // middle level, whose statuses come from resolving them through the outer index)
 hipError_t launch_shard_index(const ZgShard *shards, uint32_t n_shards, const ZgIndexSpec &spec,

@@ -1,15 +1,6 @@
-// libzgpu: host orchestration of the MI355X chunk-decode pipeline behind the C ABI of include/zgpu.h.
-//
-// A batch of chunk descriptors is planned on the host into leaf work items (a plain chunk, or one
-// inner chunk of a shard that intersects the selection), uploaded once, and decoded by a short
-// sequence of batched kernels, each over ALL items of the batch:
-//   [sharded]  k_shard_index (index chain decode + crc32c verify per shard)
-//              k_item_resolve (index lookup per item: byte range, empty -> fill, out-of-bounds)
-//   b2b stages in reverse metadata order (codec_chain.rs:612-617):
-//              crc32c verify+strip (pointer arithmetic, no copy) | gzip | zstd | unshuffle
-//   final      fused bytes(endian) + transpose + (innermost shuffle) + scatter/fill into the output
-// Per-item statuses come back in one D2H copy; the first failing item of a descriptor gives that
-// descriptor's status (try_for_each semantics, sharding_codec.rs:702-704).
+// libzgpu: host orchestration of the MI355X chunk-decode pipeline behind the C ABI of include/zgpu.h --
+// the calling thread's state (last error, counters, size detail), the C ABI, the decode call paths and
+// the coalescer. The fused plan they run lives in plan_layout.cpp (host) and plan_exec.cpp (device).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,6 +39,7 @@ int set_err(int st, const std::string &m) {
   return st;
 }
 SizeDetail &size_detail() { return g_size_detail; }
+uint64_t *call_counters() { return g_last_counters; }
 
 void zgpu::ctx_ref(zgpu_ctx *c) {
   if (c) c->refs.fetch_add(1, std::memory_order_relaxed);
@@ -85,887 +77,9 @@ hipStream_t zgpu::ctx_copy_stream(zgpu_ctx *c) {  // nullptr on failure
   return c->peer;
 }
 
-// composed permutation of all array->array codecs: encoded axis a <-> decoded axis m[a]
-void composed_axes(const Chain &c, uint32_t nd, uint32_t *m) {
-  for (uint32_t a = 0; a < nd; a++) m[a] = a;
-  for (const Codec &k : c.a2a) {  // E_{k} axis a <-> E_{k-1} axis order[a]
-    if (k.kind != CodecKind::Transpose) continue;  // the value codecs keep every element in its place
-    uint32_t t[ZG_MAXD];
-    for (uint32_t a = 0; a < nd; a++) t[a] = m[k.order[a]];
-    std::memcpy(m, t, nd * sizeof(uint32_t));
-  }
-}
-
-static void build_leaf_stages(zgpu_plan &P, const Chain &leaf, uint64_t nelem) {
-  // decode order: last b2b first
-  const int nb = (int)leaf.b2b.size();
-  int pool = 0;
-  uint64_t max_slot = 0;
-  bool fused_shuffle = false;
-  for (int i = nb - 1; i >= 0; i--) {
-    const Codec &k = leaf.b2b[i];
-    Stage s;
-    if (is_checksum(k.kind)) {
-      s.kind = checksum_stage(k.kind);
-      s.at_start = k.at_start;
-      P.stages.push_back(s);
-      continue;
-    }
-    if (k.kind == CodecKind::Shuffle && i == 0 && k.elementsize == leaf.es) {
-      fused_shuffle = true;  // fused into the scatter stage
-      continue;
-    }
-    // materialising stage: its output is the encoded representation of codecs [bytes, b2b_0..i-1]
-    int64_t out_size = (int64_t)(nelem * leaf.es);
-    for (int j = 0; j < i; j++) {
-      if (is_checksum(leaf.b2b[j].kind)) out_size += 4;
-      else if (leaf.b2b[j].kind != CodecKind::Shuffle) out_size = -1;
-      if (out_size < 0) break;
-    }
-    if (out_size < 0) throw ChainError{ZGPU_UNSUPPORTED, "a compressor nested inside another variable-size codec"};
-    s.kind = k.kind == CodecKind::Gzip    ? ST_GZIP
-             : k.kind == CodecKind::Zlib  ? ST_ZLIB
-             : k.kind == CodecKind::Bz2   ? ST_BZ2
-             : k.kind == CodecKind::Zstd  ? ST_ZSTD
-             : k.kind == CodecKind::Blosc ? ST_BLOSC
-                                          : ST_UNSHUFFLE;
-    s.elementsize = k.elementsize;
-    s.pool = pool;
-    pool ^= 1;
-    max_slot = std::max<uint64_t>(max_slot, (uint64_t)out_size);
-    P.stages.push_back(s);
-    P.n_pools = std::min(2, P.n_pools + 1);
-  }
-  P.slot_bytes = (max_slot + 255) & ~(uint64_t)255;
-  P.scatter.shuffle = fused_shuffle;
-  {
-    const char *e = std::getenv("ZGPU_UNSHUFFLE_WIDE");  // A/B knob: 1 / 2 the 16-B unshuffle (scatter.hip)
-    P.scatter.pad0 = e ? (uint32_t)std::max(0, std::min(2, std::atoi(e))) : 0u;
-  }
-}
-
-// ShardingIndex decode spec (sharding.rs:136-235, sharding_codec.rs:1262-1298): the index chain
-// must be bytes (+ crc32c), the only index_codecs zarrs' sharding writes and the GPU decodes.
-ZgIndexSpec index_spec(const Codec &sharding, uint64_t n_inner, bool validate) {
-  const Chain &xc = *sharding.index;
-  if (xc.a2b.kind != CodecKind::Bytes || !xc.a2a.empty())
-    throw ChainError{ZGPU_UNSUPPORTED, "index_codecs must be bytes (+crc32c)"};
-  for (const Codec &k : xc.b2b)
-    if (k.kind != CodecKind::Crc32c) throw ChainError{ZGPU_UNSUPPORTED, "index_codecs must be bytes (+crc32c)"};
-  if (xc.b2b.size() > 4) throw ChainError{ZGPU_UNSUPPORTED, "too many index crc32c codecs"};
-  ZgIndexSpec S{};
-  S.n_inner = n_inner;
-  S.index_bytes = (uint64_t)chain_fixed_encoded_size(xc, n_inner * 2);
-  S.at_start = sharding.at_start;
-  S.big_endian = xc.a2b.big_endian;
-  S.n_crc = (uint32_t)xc.b2b.size();
-  for (size_t k = 0; k < xc.b2b.size(); k++) S.crc_at_start[k] = xc.b2b[k].at_start;
-  S.verify = validate;
-  return S;
-}
-
-static void plan_build(zgpu_plan &P, const zgpu_chunk_desc *descs) {
-  const Chain &top = *P.chain;
-  const uint32_t nd = P.nd;
-  P.item_desc_status.assign(P.n_desc, 0);
-  if (chain_has_value_codec(top) || top.a2b.kind == CodecKind::PackBits)
-    throw ChainError{ZGPU_UNSUPPORTED, "chains with numcodecs.fixedscaleoffset, bitround or packbits do not take the "
-                                       "fused plan (zgpu_plan_create, zgpu_group_create): decode them through "
-                                       "zgpu_decode_batch / zgpu_decode_into / zgpu_decode_pinned"};
-  const bool shard_chain = top.a2b.kind == CodecKind::Sharding;
-  // transpose codecs before sharding_indexed (codec_chain.rs:557-646: the sharding codec decodes the
-  // transposed array): the shard and its inner chunk grid live in the encoded frame, encoded axis a
-  // <-> decoded axis mo[a]; descriptors are mapped into that frame and the scatter writes through
-  // output strides permuted back
-  uint32_t mo[ZG_MAXD];
-  for (uint32_t a = 0; a < nd; a++) mo[a] = a;
-  bool outer_perm = false;
-  if (shard_chain) {
-    for (const Codec &k : top.a2a)
-      if (k.kind == CodecKind::Transpose && k.order.size() != nd) throw ChainError{ZGPU_INVALID_ARGUMENT, "transpose order rank != array rank"};
-    composed_axes(top, nd, mo);
-    for (uint32_t a = 0; a < nd; a++) outer_perm = outer_perm || mo[a] != a;
-    if (!top.b2b.empty()) throw ChainError{ZGPU_UNSUPPORTED, "bytes->bytes codecs after sharding_indexed"};
-    if (top.a2b.inner_shape.size() != nd) throw ChainError{ZGPU_INVALID_ARGUMENT, "sharding chunk_shape rank"};
-  }
-  // nested sharding (sharding.rs:107-126 nested_local_subchunk_grids): the outer shard's subchunks
-  // are shards themselves ("middle" shards); their indexes are decoded on the device after the outer
-  // index resolves them, and the leaf chunks resolve through the middle indexes
-  const Chain *mid = nullptr;
-  if (shard_chain && top.a2b.inner->a2b.kind == CodecKind::Sharding) {
-    mid = top.a2b.inner.get();
-    if (!mid->a2a.empty() || !mid->b2b.empty())
-      throw ChainError{ZGPU_UNSUPPORTED, "codecs around a nested sharding_indexed"};
-    if (mid->a2b.inner->a2b.kind == CodecKind::Sharding)
-      throw ChainError{ZGPU_UNSUPPORTED, "sharding_indexed nested more than two deep"};
-    if (mid->a2b.inner_shape.size() != nd) throw ChainError{ZGPU_INVALID_ARGUMENT, "sharding chunk_shape rank"};
-  }
-  const Chain &leaf = shard_chain ? (mid ? *mid->a2b.inner : *top.a2b.inner) : top;
-  P.leaf = &leaf;
-  P.sharded = shard_chain;
-  P.nested = mid != nullptr;
-  for (const Codec &k : leaf.a2a)
-    if (k.kind == CodecKind::Transpose && k.order.size() != nd) throw ChainError{ZGPU_INVALID_ARGUMENT, "transpose order rank != array rank"};
-
-  // leaf chunk shape
-  uint64_t leaf_shape[ZG_MAXD];
-  uint64_t mid_shape[ZG_MAXD], cps2[ZG_MAXD], n_inner2 = 1;  // nested: middle shard shape, its subchunks
-  if (shard_chain) {
-    for (uint32_t d = 0; d < nd; d++) leaf_shape[d] = (mid ? mid->a2b.inner_shape : top.a2b.inner_shape)[d];
-    for (uint32_t d = 0; d < nd; d++) mid_shape[d] = top.a2b.inner_shape[d];
-    if (mid) {
-      for (uint32_t d = 0; d < nd; d++) {
-        if (!leaf_shape[d] || mid_shape[d] % leaf_shape[d])
-          throw ChainError{ZGPU_INVALID_ARGUMENT, "nested sharding: subchunk shape does not divide the shard"};
-        cps2[d] = mid_shape[d] / leaf_shape[d];
-        n_inner2 *= cps2[d];
-      }
-    }
-  } else if (P.n_desc) {
-    for (uint32_t d = 0; d < nd; d++) leaf_shape[d] = descs[0].chunk_shape[d];
-  } else {
-    for (uint32_t d = 0; d < nd; d++) leaf_shape[d] = 1;
-  }
-  uint64_t nelem = 1;
-  for (uint32_t d = 0; d < nd; d++) nelem *= leaf_shape[d];
-
-  uint64_t out_strides[ZG_MAXD], s = 1;
-  for (int d = (int)nd - 1; d >= 0; d--) {
-    out_strides[d] = s;
-    s *= P.out_shape[d];
-  }
-  const uint64_t es = top.es;
-  uint64_t max_sel[ZG_MAXD] = {0};
-  uint64_t n_inner = 1, cps[ZG_MAXD];
-  if (shard_chain) {
-    int64_t isz = -1;
-    for (uint32_t d = 0; d < nd; d++) cps[d] = 0;
-    (void)isz;
-  }
-
-  for (uint64_t i = 0; i < P.n_desc; i++) {
-    const zgpu_chunk_desc &D = descs[i];
-    bool ok = true, full = true;
-    for (uint32_t d = 0; d < nd; d++) {
-      if (D.sel_start[d] + D.sel_shape[d] > D.chunk_shape[d] ||
-          D.out_start[d] + D.sel_shape[d] > P.out_shape[d])
-        ok = false;
-      if (D.sel_start[d] != 0 || D.sel_shape[d] != D.chunk_shape[d]) full = false;
-      if (!shard_chain && D.chunk_shape[d] != leaf_shape[d]) ok = false;
-    }
-    if (!ok) {
-      P.item_desc_status[i] = ZGPU_INVALID_ARGUMENT;
-      continue;
-    }
-    uint64_t vol = 1;
-    for (uint32_t d = 0; d < nd; d++) vol *= D.sel_shape[d];
-    if (vol == 0 && (!full || shard_chain)) continue;  // a zero-extent full chunk still runs its checks
-    P.alg_bytes_static += vol * es;
-    if (!shard_chain) {
-      ZgItem it{};
-      it.src = (uint64_t)D.enc;
-      it.len = D.enc_len;
-      it.desc = (uint32_t)i;
-      it.flags = (D.enc ? 0u : ZG_ITEM_FILL) | (full ? 0u : ZG_ITEM_PARTIAL);
-      if (D.enc) P.alg_bytes_static += D.enc_len;
-      P.items.push_back(it);
-      for (uint32_t d = 0; d < nd; d++) P.geom.push_back(D.sel_start[d]);
-      for (uint32_t d = 0; d < nd; d++) P.geom.push_back(D.sel_shape[d]);
-      for (uint32_t d = 0; d < nd; d++) P.geom.push_back(D.out_start[d]);
-      for (uint32_t d = 0; d < nd; d++) max_sel[d] = std::max(max_sel[d], D.sel_shape[d]);
-      continue;
-    }
-    // sharded descriptor: one item per intersecting inner chunk, in the sharding codec's (encoded)
-    // frame: axis a is decoded axis mo[a]
-    uint64_t c_sh[ZG_MAXD], c_ss[ZG_MAXD], c_sz[ZG_MAXD], c_os[ZG_MAXD];
-    for (uint32_t a = 0; a < nd; a++) {
-      c_sh[a] = D.chunk_shape[mo[a]];
-      c_ss[a] = D.sel_start[mo[a]];
-      c_sz[a] = D.sel_shape[mo[a]];
-      c_os[a] = D.out_start[mo[a]];
-    }
-    // subchunks of the (outer) shard: the leaf chunks, or the middle shards when nested
-    const uint64_t *sub_shape = mid ? mid_shape : leaf_shape;
-    n_inner = 1;
-    for (uint32_t d = 0; d < nd; d++) {
-      if (c_sh[d] % sub_shape[d]) ok = false;
-      cps[d] = c_sh[d] / sub_shape[d];
-      n_inner *= cps[d];
-    }
-    if (!ok) {  // calculate_chunks_per_shard error (sharding.rs:136-154)
-      P.item_desc_status[i] = ZGPU_INVALID_ARGUMENT;
-      continue;
-    }
-    if (P.ispec.n_inner && P.ispec.n_inner != n_inner) {
-      P.item_desc_status[i] = ZGPU_UNSUPPORTED;  // mixed shard shapes in one batch
-      continue;
-    }
-    P.ispec.n_inner = n_inner;
-    const uint32_t shard_slot = (uint32_t)P.shards.size();
-    P.shards.push_back(ZgShard{(uint64_t)D.enc, D.enc ? D.enc_len : 0});
-    uint64_t lo[ZG_MAXD], hi[ZG_MAXD], idx[ZG_MAXD];
-    // one leaf item per intersecting leaf chunk; `sub` (nested: the middle shard, its index slot,
-    // its selection [m0, m1) and output origin mo0) or the outer shard itself
-    auto add_leaves = [&](uint32_t slot, const uint64_t *m0, const uint64_t *m1, const uint64_t *mo0,
-                          const uint64_t *grid) {
-      uint64_t llo[ZG_MAXD], lhi[ZG_MAXD], li[ZG_MAXD];
-      for (uint32_t d = 0; d < nd; d++) {
-        llo[d] = m0[d] / leaf_shape[d];
-        lhi[d] = (m1[d] - 1) / leaf_shape[d] + 1;
-        li[d] = llo[d];
-      }
-      for (;;) {
-        uint64_t lin = 0;
-        ZgItem it{};
-        it.desc = (uint32_t)i;
-        it.shard = slot;
-        it.flags = D.enc ? (ZG_ITEM_SHARDED | (full ? 0u : ZG_ITEM_PARTIAL)) : ZG_ITEM_FILL;
-        uint64_t g[3 * ZG_MAXD];
-        for (uint32_t d = 0; d < nd; d++) {
-          lin = lin * grid[d] + li[d];
-          const uint64_t cs = li[d] * leaf_shape[d], ce = cs + leaf_shape[d];
-          const uint64_t s0 = std::max(m0[d], cs), s1 = std::min(m1[d], ce);
-          g[d] = s0 - cs;
-          g[nd + d] = s1 - s0;
-          g[2 * nd + d] = mo0[d] + (s0 - m0[d]);
-          max_sel[d] = std::max(max_sel[d], s1 - s0);
-        }
-        it.inner = (uint32_t)lin;
-        P.items.push_back(it);
-        P.geom.insert(P.geom.end(), g, g + 3 * nd);
-        int d = (int)nd - 1;
-        for (; d >= 0; d--) {
-          if (++li[d] < lhi[d]) break;
-          li[d] = llo[d];
-        }
-        if (d < 0) break;
-      }
-    };
-    if (!mid) {
-      uint64_t m1[ZG_MAXD];
-      for (uint32_t d = 0; d < nd; d++) m1[d] = c_ss[d] + c_sz[d];
-      add_leaves(shard_slot, c_ss, m1, c_os, cps);
-      continue;
-    }
-    if (P.ispec2.n_inner && P.ispec2.n_inner != n_inner2) {
-      P.item_desc_status[i] = ZGPU_UNSUPPORTED;
-      continue;
-    }
-    P.ispec2.n_inner = n_inner2;
-    for (uint32_t d = 0; d < nd; d++) {
-      lo[d] = c_ss[d] / mid_shape[d];
-      hi[d] = (c_ss[d] + c_sz[d] - 1) / mid_shape[d] + 1;
-      idx[d] = lo[d];
-    }
-    for (;;) {  // every intersecting middle shard: an index slot, then its leaf chunks
-      uint64_t lin = 0, m0[ZG_MAXD], m1[ZG_MAXD], mo0[ZG_MAXD];
-      for (uint32_t d = 0; d < nd; d++) {
-        lin = lin * cps[d] + idx[d];
-        const uint64_t cs = idx[d] * mid_shape[d], ce = cs + mid_shape[d];
-        const uint64_t s0 = std::max(c_ss[d], cs), s1 = std::min(c_ss[d] + c_sz[d], ce);
-        m0[d] = s0 - cs;
-        m1[d] = s1 - cs;
-        mo0[d] = c_os[d] + (s0 - c_ss[d]);
-      }
-      const uint32_t mslot = (uint32_t)P.mids.size();
-      ZgItem mi{};
-      mi.desc = (uint32_t)i;
-      mi.shard = shard_slot;
-      mi.inner = (uint32_t)lin;
-      mi.flags = D.enc ? ZG_ITEM_SHARDED : ZG_ITEM_FILL;
-      P.mids.push_back(mi);
-      add_leaves(mslot, m0, m1, mo0, cps2);
-      int d = (int)nd - 1;
-      for (; d >= 0; d--) {
-        if (++idx[d] < hi[d]) break;
-        idx[d] = lo[d];
-      }
-      if (d < 0) break;
-    }
-  }
-
-  if (shard_chain) {
-    P.ispec = index_spec(top.a2b, P.ispec.n_inner, P.validate);
-    for (const ZgShard &sh : P.shards)
-      if (sh.ptr) P.alg_bytes_static += P.ispec.index_bytes;
-    if (mid) {
-      P.ispec2 = index_spec(mid->a2b, n_inner2, P.validate);
-      for (const ZgItem &m : P.mids)
-        if (!(m.flags & ZG_ITEM_FILL)) P.alg_bytes_static += P.ispec2.index_bytes;
-    }
-  }
-
-  build_leaf_stages(P, leaf, nelem);
-
-  // scatter parameters
-  ZgScatter &S = P.scatter;
-  S.nd = nd;
-  S.es = leaf.es;
-  S.comp = leaf.comp;
-  S.swap = leaf.a2b.big_endian && leaf.comp > 1;
-  S.nelem = nelem;
-  std::memcpy(S.fill, leaf.fill, 16);
-  uint32_t m[ZG_MAXD];
-  composed_axes(leaf, nd, m);
-  uint64_t eshape[ZG_MAXD], est[ZG_MAXD];
-  for (uint32_t a = 0; a < nd; a++) eshape[a] = leaf_shape[m[a]];
-  s = 1;
-  for (int a = (int)nd - 1; a >= 0; a--) {
-    est[a] = s;
-    s *= eshape[a];
-  }
-  for (uint32_t a = 0; a < nd; a++) S.enc_stride[m[a]] = est[a];
-  for (uint32_t d = 0; d < nd; d++) {
-    S.chunk_shape[d] = leaf_shape[d];
-    S.out_stride[d] = out_strides[mo[d]];
-  }
-  S.tile_a = m[nd - 1];
-  S.tile_b = ZG_MAXD;
-  for (uint32_t d = 0; d + 1 < nd; d++) {
-    if (d == S.tile_a) continue;
-    if (S.tile_b == ZG_MAXD || S.enc_stride[d] <= S.enc_stride[S.tile_b]) S.tile_b = d;
-  }
-  if (outer_perm && S.out_stride[nd - 1] != 1) {
-    P.scatter_mode = SCATTER_GENERIC;  // the row / tile kernels write unit-stride output rows
-  } else if (S.tile_a == nd - 1) {
-    P.scatter_mode = SCATTER_ROWS;
-  } else if (!S.shuffle && (S.es == 1 || S.es == 2 || S.es == 4 || S.es == 8)) {
-    P.scatter_mode = SCATTER_TILED;
-  } else {
-    P.scatter_mode = SCATTER_GENERIC;
-  }
-  P.scatter_units = P.items.empty() ? 0 : scatter_units_per_item(P.scatter_mode, S, max_sel);
-  if (P.scatter_mode == SCATTER_TILED && !P.items.empty()) {
-    P.origin.resize(P.items.size());
-    P.tiled_p = tiled_persistent_params(S, P.geom.data(), P.items.size(), P.tiled_q, P.origin.data()) &&
-                P.tiled_q.upi == P.scatter_units && tiled_persistent_fits(P.items.size(), P.tiled_q.upi);
-    if (!P.tiled_p) P.origin.clear();
-  }
-  P.last_path = P.tiled_p ? ZGPU_SCATTER_TILED_PERSISTENT : P.scatter_mode;
-
-  // blosc as the last stage feeding the rows scatter unchanged (no swap / shuffle / transpose), every
-  // decoded item a whole chunk on 16-B aligned output rows: k_blosc_finish writes the rows itself
-  if (!P.stages.empty() && P.stages.back().kind == ST_BLOSC && P.scatter_mode == SCATTER_ROWS && !S.swap &&
-      !S.shuffle && S.nelem > 0 && S.out_stride[nd - 1] == 1 && (S.chunk_shape[nd - 1] * S.es) % 16 == 0) {
-    bool ok = true;
-    uint64_t st = 1;
-    for (int a = (int)nd - 1; a >= 0 && ok; a--) {
-      ok = S.enc_stride[a] == st && (a == (int)nd - 1 || (S.out_stride[a] * S.es) % 16 == 0);
-      st *= S.chunk_shape[a];
-    }
-    for (size_t i = 0; i < P.items.size() && ok; i++) {
-      if (P.items[i].flags & ZG_ITEM_FILL) continue;
-      const uint64_t *g = P.geom.data() + i * 3 * nd;
-      for (uint32_t d = 0; d < nd && ok; d++) ok = g[d] == 0 && g[nd + d] == S.chunk_shape[d];
-      ok = ok && (g[2 * nd + nd - 1] * S.es) % 16 == 0;
-    }
-    P.bl_direct = ok && !std::getenv("ZGPU_BLOSC_NO_DIRECT");
-  }
-  // gzip as the last stage feeding the rows scatter unchanged (no swap / shuffle / transpose), rows of a
-  // power-of-two multiple of 16 bytes, the row axes but the outermost of power-of-two extent: k_gzip
-  // writes the items whose selection is their whole chunk into the output rows itself and the scatter
-  // takes only the others (C3: the subset's 12,167 interior inner chunks of 15,625). ZGPU_GZIP_DIRECT=0: off.
-  {
-    const char *gz_env = std::getenv("ZGPU_GZIP_DIRECT");  // read per plan (an A/B knob)
-    const bool gz_on = !gz_env || std::atoi(gz_env) != 0;
-    const uint64_t Lb = S.chunk_shape[nd - 1] * S.es;
-    bool ok = gz_on && !P.stages.empty() && P.stages.back().kind == ST_GZIP && P.scatter_mode == SCATTER_ROWS &&
-              !S.swap && !S.shuffle && S.nelem > 0 && nd >= 1 && nd <= 3 && S.out_stride[nd - 1] == 1 && Lb >= 16 &&
-              (nd < 2 || S.out_stride[0] * S.es < (1ull << 32)) && S.nelem * S.es < (1ull << 32) &&
-              (Lb & (Lb - 1)) == 0;
-    uint64_t st = 1;
-    for (int a = (int)nd - 1; a >= 0 && ok; a--) {
-      ok = S.enc_stride[a] == st && (a == (int)nd - 1 || (S.out_stride[a] * S.es) % 16 == 0) &&
-           (a == 0 || a == (int)nd - 1 || (S.chunk_shape[a] & (S.chunk_shape[a] - 1)) == 0);
-      st *= S.chunk_shape[a];
-    }
-    P.gz_direct = ok;
-    if (ok) {
-      P.gz.want = S.nelem * S.es;
-      P.gz.nd = nd;
-      P.gz.lbs = (uint32_t)__builtin_ctzll(Lb);
-      for (uint32_t d = 0; d < nd; d++) {
-        P.gz.cshape[d] = S.chunk_shape[d];
-        P.gz.ostr[d] = S.out_stride[d] * S.es;
-      }
-    }
-  }
-  // blosc feeding the scatter directly (its decoded bytes are the chunk's encoded-layout elements; a
-  // fused unshuffle would interleave planes): a partial selection needs only the byte range between
-  // its first and last element in the encoded layout, so only the blocks that cover it are decoded,
-  // as the reference's blosc partial decoder does (blosc_partial_decoder.rs:33-60 ->
-  // blosc_decompress_bytes_partial, c-blosc's blosc_getitem)
-  if (!P.stages.empty() && P.stages.back().kind == ST_BLOSC && !S.shuffle && !std::getenv("ZGPU_BLOSC_NO_PARTIAL")) {
-    bool any = false;
-    P.bl_need.assign(2 * P.items.size(), 0);
-    for (size_t i = 0; i < P.items.size(); i++) {
-      P.bl_need[2 * i + 1] = UINT64_MAX;
-      if (!(P.items[i].flags & ZG_ITEM_PARTIAL)) continue;
-      const uint64_t *g = P.geom.data() + i * 3 * nd;
-      uint64_t lo = 0, hi = 0;
-      bool empty = false;
-      for (uint32_t d = 0; d < nd; d++) {
-        if (!g[nd + d]) empty = true;
-        lo += g[d] * S.enc_stride[d];
-        hi += (g[d] + g[nd + d] - 1) * S.enc_stride[d];
-      }
-      if (empty) continue;
-      P.bl_need[2 * i] = lo * S.es;
-      P.bl_need[2 * i + 1] = (hi + 1) * S.es;
-      any = true;
-    }
-    if (!any) P.bl_need.clear();
-  }
-}
-
-void plan_upload(zgpu_plan &P, hipStream_t us) {
-  const size_t ni = P.items.size();
-  if (ni) {
-    P.d_items = P.mem.dev<ZgItem>(ni);
-    P.d_items_init = P.mem.dev<ZgItem>(ni);
-    P.d_geom = P.mem.dev<uint64_t>(P.geom.size());
-    HIPCHK(hipMemcpyAsync(P.d_items_init, P.items.data(), ni * sizeof(ZgItem), hipMemcpyHostToDevice, us));
-    HIPCHK(hipMemcpyAsync(P.d_geom, P.geom.data(), P.geom.size() * 8, hipMemcpyHostToDevice, us));
-    for (int k = 0; k < P.n_pools; k++) P.d_pool[k] = P.mem.dev<uint8_t>(ni * P.slot_bytes);
-    if (!P.bl_need.empty()) {
-      P.d_bl_need = P.mem.dev<uint64_t>(P.bl_need.size());
-      HIPCHK(hipMemcpyAsync(P.d_bl_need, P.bl_need.data(), P.bl_need.size() * 8, hipMemcpyHostToDevice, us));
-    }
-    for (const Stage &s : P.stages) {
-      if ((s.kind == ST_GZIP || s.kind == ST_ZLIB) && !P.d_order) {
-        P.d_order = P.mem.dev<uint32_t>(ni);
-        if (const uint64_t b = gzip_seg_scratch_bytes((uint32_t)ni)) P.d_gz_seg = (uint32_t *)P.mem.dev<uint8_t>(b);
-      }
-      if (s.kind == ST_BZ2 && !P.bz.base) {
-        // 5 x slot_bytes of BWT vector (+ 1.25 x of bytes before RLE1, + block records) per item: a batch
-        // whose scratch passes the budget (ZGPU_BZ2_SCRATCH_MB, read per plan; default 8192) runs in rounds
-        P.bz.item_bytes = bz2_item_scratch_bytes(P.slot_bytes, P.bz.cap, P.bz.tt_cap);
-        const char *e = std::getenv("ZGPU_BZ2_SCRATCH_MB");
-        const uint64_t mb = e ? std::strtoull(e, nullptr, 10) : 0;
-        const uint64_t budget = (mb ? mb : 8192) << 20;
-        uint64_t per_round = std::max<uint64_t>(1, budget / P.bz.item_bytes);
-        per_round = std::min<uint64_t>(per_round, std::max<uint64_t>(1, (1u << 30) / P.bz.cap));
-        P.bz.round_items = (uint32_t)std::min<uint64_t>(per_round, ni);
-        const uint64_t items_bytes = P.bz.round_items * P.bz.item_bytes;  // a multiple of 256
-        P.bz.base = P.mem.dev<uint8_t>(items_bytes + bz2_list_bytes(P.bz.round_items, P.bz.cap));
-        P.bz.lists = (uint32_t *)(P.bz.base + items_bytes);
-      }
-      if (s.kind == ST_ZSTD && !P.zs.blks) {
-        uint64_t blk_bytes;
-        zstd_scratch_layout(P.slot_bytes, P.zs.blk_cap, blk_bytes, P.zs.lit_stride, P.zs.seq_cap);
-        P.zs.blks = P.mem.dev<uint8_t>(ni * (uint64_t)P.zs.blk_cap * blk_bytes);
-        P.zs.norm = (int16_t *)P.mem.dev<uint8_t>(ni * (uint64_t)P.zs.blk_cap * zstd_norm_bytes());
-        P.zs.nblk = P.mem.dev<uint32_t>(ni);
-        P.zs.mode = P.mem.dev<uint32_t>(ni);
-        P.zs.lit = P.mem.dev<uint8_t>(ni * P.zs.lit_stride);
-        P.zs.seq = P.mem.dev<uint32_t>(ni * P.zs.seq_cap * 3);
-        P.d_zser = P.mem.dev<uint32_t>(ni);
-        P.zs.ser_list = P.d_zser;
-        if (const uint64_t rb = zstd_lit_rec_bytes(P.zs.lit_rec_wgs)) P.zs.lit_rec = P.mem.dev<uint8_t>(rb);
-        static const uint64_t par_max = [] {  // ZGPU_ZSTD_XPAR_MB: the latency mode's batch limit (tuning)
-          const char *e = std::getenv("ZGPU_ZSTD_XPAR_MB");
-          return e ? (uint64_t)std::strtoull(e, nullptr, 10) << 20 : ZPAR_MAX_BYTES;
-        }();
-        if (ni * P.slot_bytes <= par_max) {  // the window executor's latency mode (few frames)
-          P.zs.ext = P.mem.dev<uint32_t>(2 * ni * P.slot_bytes);
-          P.zs.ext_cnt = P.mem.dev<unsigned long long>(ZEXT_ROUNDS);
-          P.zs.ext_items = ni;
-        }
-      }
-    }
-  }
-  // the longest encoded item: known for plain chunks; an inner chunk's length comes from its shard's
-  // index on the device, so the chain's bound stands in for it (no more than the longest shard)
-  P.in_len_hint = 0;
-  if (P.sharded) {
-    uint64_t shard_max = 0;
-    for (const ZgShard &sh : P.shards) shard_max = std::max(shard_max, sh.len);
-    const int64_t b = P.leaf ? chain_encoded_bound(*P.leaf, P.scatter.nelem) : -1;
-    P.in_len_hint = b >= 0 ? std::min<uint64_t>((uint64_t)b, shard_max) : shard_max;
-  } else {
-    for (const ZgItem &it : P.items) P.in_len_hint = std::max(P.in_len_hint, it.len);
-  }
-  // one scratch for every checksum stage of the plan, sized for the longest input any of them can be
-  // given a hint of (the stages run one after another on the plan's stream)
-  for (const Stage &s : P.stages)
-    if (ni && (s.kind == ST_ADLER32 || s.kind == ST_FLETCHER32))
-      P.grow(P.ck_parts, linsum_scratch_bytes((uint32_t)ni, std::max(P.in_len_hint, P.slot_bytes)));
-  P.ctl_bytes = 256 + ni * 4;
-  P.d_ctl = P.mem.dev<uint8_t>(P.ctl_bytes);
-  P.h_ctl = P.mem.pinned<uint8_t>(P.ctl_bytes);
-  if (P.tiled_p) {
-    P.d_origin = P.mem.dev<uint64_t>(ni);
-    HIPCHK(hipMemcpyAsync(P.d_origin, P.origin.data(), ni * 8, hipMemcpyHostToDevice, us));
-  }
-  P.d_counter = (unsigned long long *)P.d_ctl;
-  P.d_status = (uint32_t *)(P.d_ctl + 256);
-  P.zs.counters = P.d_counter + CTR_ZSTD_SERIAL;
-  P.zs.lat_count = P.d_counter + CTR_ZSTD_LATENCY;
-  P.zs.ser_count = P.d_counter + CTR_ZSTD_NSER;
-  P.zs.max_nblk = P.d_counter + CTR_ZSTD_MAXBLK;
-  if (const char *e = std::getenv("ZGPU_ZSTD_FORCE_SERIAL")) P.zs.force_serial = std::atoi(e) != 0;
-  if (!P.shards.empty()) {
-    P.d_shards = P.mem.dev<ZgShard>(P.shards.size());
-    P.d_index = P.mem.dev<uint64_t>(P.shards.size() * P.ispec.n_inner * 2);
-    P.d_shard_status = P.mem.dev<uint32_t>(P.shards.size());
-    HIPCHK(hipMemcpyAsync(P.d_shards, P.shards.data(), P.shards.size() * sizeof(ZgShard), hipMemcpyHostToDevice,
-                          us));
-  }
-  if (!P.mids.empty()) {
-    const size_t nm = P.mids.size();
-    P.d_mids = P.mem.dev<ZgItem>(nm);
-    P.d_mids_init = P.mem.dev<ZgItem>(nm);
-    P.d_mid_status = P.mem.dev<uint32_t>(nm);
-    P.d_shard_status2 = P.mem.dev<uint32_t>(nm);
-    P.d_mid_shards = P.mem.dev<ZgShard>(nm);
-    P.d_index2 = P.mem.dev<uint64_t>(nm * P.ispec2.n_inner * 2);
-    HIPCHK(hipMemcpyAsync(P.d_mids_init, P.mids.data(), nm * sizeof(ZgItem), hipMemcpyHostToDevice, us));
-  }
-}
-
-// blosc stage: frame headers -> stream table layout -> streams + blocks on the device -> zstd / lz4 /
-// blosclz stream decode -> per-block gather + unshuffle into the item slots. The first execution of a
-// plan reads the headers back to size the table (the one host round trip of any stage) and records
-// the sizes as capacities; later executions lay the table out on the device against them
-// (k_blosc_layout) and stay asynchronous. A later input that outgrows them is re-run by plan_statuses.
-static void blosc_stage(zgpu_plan &P, const Stage &st, uint8_t *out, hipStream_t s) {
-  const uint32_t ni = (uint32_t)P.items.size();
-  uint8_t *dst = P.d_pool[st.pool];
-  BlInfo *info = (BlInfo *)P.grow(P.bl_info, ni * sizeof(BlInfo));
-  HIPCHK(launch_blosc_info(P.d_items, P.d_status, ni, P.slot_bytes, info, s));
-  uint64_t *d_bases = (uint64_t *)P.grow(P.bl_bases, ni * 16);
-  BlDecode D{};
-  D.bases = d_bases;
-  if (P.bl_direct && ((uintptr_t)out & 15) == 0) {
-    D.dout = out;
-    D.geom = P.d_geom;
-    D.sc = P.scatter;
-  }
-  D.ovf = P.d_counter + CTR_BLOSC_OVF;
-  D.need = P.d_bl_need;
-  D.blocks_decoded = P.d_counter + CTR_BLOSC_BLOCKS;
-  BlCaps &caps = P.bl_caps;
-  const bool cached = P.bl_caps_valid;
-  if (!cached) {
-    if (!P.bl_h) P.bl_h = (uint8_t *)P.mem.pinned<BlInfo>(ni);  // (a plan's item count is fixed)
-    HIPCHK(hipMemcpyAsync(P.bl_h, info, ni * sizeof(BlInfo), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<BlInfo> hi(ni);
-    std::memcpy(hi.data(), P.bl_h, ni * sizeof(BlInfo));
-    BlCaps exact{0, 0, 0, 0};
-    for (uint32_t i = 0; i < ni; i++) {
-      if (hi[i].comp == BL_COMP_SKIP) continue;
-      exact.n_sub += hi[i].nsub;
-      exact.n_blk += hi[i].nblk;
-      if (hi[i].nsub)
-        exact.kinds |= hi[i].comp == BL_COMP_ZSTD ? BL_HAS_ZSTD : hi[i].comp == BL_COMP_LZ4 ? BL_HAS_LZ4
-                       : hi[i].comp == BL_COMP_BLOSCLZ ? BL_HAS_BLOSCLZ : hi[i].comp == BL_COMP_ZLIB ? BL_HAS_ZLIB
-                       : hi[i].comp == BL_COMP_SNAPPY ? BL_HAS_SNAPPY : 0u;
-      exact.max_ne = std::max<uint64_t>(exact.max_ne, hi[i].max_ne);
-    }
-    // capacities only grow (a plan whose inputs alternate between layouts settles on their maximum)
-    if (P.bl_caps_seen) {
-      caps.n_sub = std::max(caps.n_sub, exact.n_sub);
-      caps.n_blk = std::max(caps.n_blk, exact.n_blk);
-      caps.max_ne = std::max(caps.max_ne, exact.max_ne);
-      caps.kinds |= exact.kinds;
-    } else {
-      caps = exact;
-    }
-    P.bl_caps_seen = P.bl_caps_valid = true;
-  }
-  D.n_sub = caps.n_sub;
-  D.n_blk = caps.n_blk;
-  D.n_zstd = caps.kinds & BL_HAS_ZSTD;
-  D.n_lz4 = caps.kinds & BL_HAS_LZ4;
-  D.n_blosclz = caps.kinds & BL_HAS_BLOSCLZ;
-  D.n_zlib = caps.kinds & BL_HAS_ZLIB;
-  D.n_snappy = caps.kinds & BL_HAS_SNAPPY;
-  const uint64_t ns = std::max<uint64_t>(D.n_sub, 1);
-  D.subs = (ZgItem *)P.grow(P.bl_subs, ns * sizeof(ZgItem));
-  D.sub_status = (uint32_t *)P.grow(P.bl_sub_status, ns * 4);
-  D.sub_kind = (uint32_t *)P.grow(P.bl_sub_kind, ns * 4);
-  D.blocks = (BlBlock *)P.grow(P.bl_blocks, std::max<uint64_t>(D.n_blk, 1) * sizeof(BlBlock));
-  if (D.n_zstd + D.n_lz4 + D.n_blosclz + D.n_zlib + D.n_snappy) {
-    D.sub_slot = (caps.max_ne + 255) & ~(uint64_t)255;
-    D.tmp = (uint8_t *)P.grow(P.bl_tmp, D.n_sub * D.sub_slot);
-  }
-  if (D.n_zlib) {
-    D.zaux = (uint2 *)P.grow(P.bl_zaux, D.n_sub * sizeof(uint2));
-    if (const uint64_t b = gzip_seg_scratch_bytes((uint32_t)D.n_sub)) D.zseg = (uint32_t *)P.grow(P.bl_zseg, b);
-  }
-  D.lz_list = (D.n_lz4 || D.n_blosclz || D.n_snappy) ? (uint32_t *)P.grow(P.bl_lzl, 2 * (D.n_sub + 1) * 4) : nullptr;
-  if (D.n_zstd) {
-    uint64_t blk_bytes;
-    zstd_scratch_layout(D.sub_slot, D.zs.blk_cap, blk_bytes, D.zs.lit_stride, D.zs.seq_cap);
-    D.zs.blks = P.grow(P.bl_zblks, D.n_sub * (uint64_t)D.zs.blk_cap * blk_bytes);
-    D.zs.norm = (int16_t *)P.grow(P.bl_znorm, D.n_sub * (uint64_t)D.zs.blk_cap * zstd_norm_bytes());
-    D.zs.nblk = (uint32_t *)P.grow(P.bl_znblk, D.n_sub * 4);
-    D.zs.mode = (uint32_t *)P.grow(P.bl_zmode, D.n_sub * 4);
-    D.zs.lit = (uint8_t *)P.grow(P.bl_zlit, D.n_sub * D.zs.lit_stride);
-    D.zs.seq = (uint32_t *)P.grow(P.bl_zseq, D.n_sub * D.zs.seq_cap * 12);
-    D.zs.counters = P.zs.counters;
-    D.zs.max_nblk = P.zs.max_nblk;
-    D.zs.force_serial = P.zs.force_serial;
-    D.zs.ser_list = (uint32_t *)P.grow(P.bl_zser, D.n_sub * 4);
-    if (const uint64_t rb = zstd_lit_rec_bytes(D.zs.lit_rec_wgs)) D.zs.lit_rec = (uint8_t *)P.grow(P.bl_zrec, rb);
-    // k_blosc_finish reads raw / rle / literal-only zstd blocks where they lie (ZGPU_BLOSC_ALIAS=0: off)
-    const char *ae = std::getenv("ZGPU_BLOSC_ALIAS");  // read per call (tests switch it)
-    const bool alias_on = !ae || std::atoi(ae) != 0;
-    D.zs.alias = alias_on ? (uint64_t *)P.grow(P.bl_zalias, D.n_sub * 3 * ZALIAS * 8) : nullptr;
-    D.zs.ser_count = P.zs.ser_count;
-    D.zs.launch_serial = P.zs.launch_serial;
-    P.zstd_fork(D.zs, s);
-    P.zstd_split(D.zs, s);
-  }
-  // the layout (bases, inert tails past this execution's totals) is always computed on the device
-  HIPCHK(launch_blosc_layout(info, ni, d_bases, caps, D, s));
-  HIPCHK(launch_blosc_decode(P.d_items, P.d_status, ni, info, D, dst, P.slot_bytes, s));
-}
-
-// Enqueue the decode of an uploaded plan on stream s.
-void plan_enqueue(zgpu_plan &P, uint8_t *out, hipStream_t s) {
-  const uint32_t ni = (uint32_t)P.items.size();
-  P.last_out = out;
-  P.bz_rounds = 0;
-  HIPCHK(hipMemsetAsync(P.d_ctl, 0, P.ctl_bytes, s));
-  if (!ni) return;
-  P.zs.launch_serial = P.zstd_serial_off ? 0u : 1u;
-  P.zstd_serial_skipped = P.zstd_serial_off;
-  // stages rewrite each item's {src,len} in place; a chain with none reads the uploaded table as is
-  const bool mutates = P.sharded || !P.stages.empty();
-  ZgItem *items = mutates ? P.d_items : P.d_items_init;
-  if (mutates)
-    HIPCHK(hipMemcpyAsync(P.d_items, P.d_items_init, ni * sizeof(ZgItem), hipMemcpyDeviceToDevice, s));
-  if (P.sharded) {
-    HIPCHK(launch_shard_index(P.d_shards, (uint32_t)P.shards.size(), P.ispec, P.d_index, P.d_shard_status, 0, s));
-    if (P.nested && !P.mids.empty()) {
-      // middle shards: resolved through the outer index, their indexes decoded, then the leaves
-      // resolve through them (a middle-shard error reaches every leaf of it via its status)
-      const uint32_t nm = (uint32_t)P.mids.size();
-      HIPCHK(hipMemcpyAsync(P.d_mids, P.d_mids_init, nm * sizeof(ZgItem), hipMemcpyDeviceToDevice, s));
-      HIPCHK(hipMemsetAsync(P.d_mid_status, 0, nm * 4, s));
-      HIPCHK(launch_item_resolve(P.d_mids, P.d_mid_status, nm, P.d_shards, P.d_index, P.d_shard_status,
-                                 P.ispec.n_inner, P.d_counter + CTR_SCRATCH, s));
-      HIPCHK(launch_mid_shards(P.d_mids, P.d_mid_status, nm, P.d_mid_shards, P.d_shard_status2, s));
-      HIPCHK(launch_shard_index(P.d_mid_shards, nm, P.ispec2, P.d_index2, P.d_shard_status2, 1, s));
-      HIPCHK(launch_item_resolve(P.d_items, P.d_status, ni, P.d_mid_shards, P.d_index2, P.d_shard_status2,
-                                 P.ispec2.n_inner, P.d_counter + CTR_ENC_BYTES, s));
-    } else if (!P.nested) {
-      HIPCHK(launch_item_resolve(P.d_items, P.d_status, ni, P.d_shards, P.d_index, P.d_shard_status, P.ispec.n_inner,
-                                 P.d_counter, s));
-    }
-  }
-  int crc_tail = 0;  // a trailing crc32c stage handed to the next gzip stage (launch_gzip places it)
-  bool wrote_direct = false;  // a stage wrote whole items into the output (the scatter lists the rest)
-  uint64_t len_hint = P.in_len_hint;  // of the current stage's input (a slot after a materialising stage)
-  for (size_t si = 0; si < P.stages.size(); si++) {
-    const Stage &st = P.stages[si];
-    switch (st.kind) {
-      case ST_ADLER32:
-      case ST_FLETCHER32: {
-        HIPCHK(launch_linsum_strip(st.kind == ST_ADLER32 ? CK_ADLER32 : CK_FLETCHER32, P.d_items, P.d_status, ni,
-                                   st.at_start, P.validate ? 1 : 0, len_hint, P.ck_parts.p, s));  // sized in plan_upload
-        break;
-      }
-      case ST_ZLIB:
-        HIPCHK(launch_zlib_items(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.slot_bytes, P.d_order, P.d_gz_seg,
-                                 s));
-        break;
-      case ST_BZ2:
-        P.bz.blocks = P.d_counter + CTR_BZ2_BLOCKS;
-        P.bz_rounds += (ni + P.bz.round_items - 1) / P.bz.round_items;
-        HIPCHK(launch_bz2(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.slot_bytes, P.bz, s));
-        break;
-      case ST_CRC32C:
-        if (!st.at_start && si + 1 < P.stages.size() && P.stages[si + 1].kind == ST_GZIP && P.d_gz_seg) {
-          crc_tail = P.validate ? 1 : 2;
-          break;
-        }
-        HIPCHK(launch_crc32c_strip(P.d_items, P.d_status, ni, st.at_start, P.validate ? 1 : 0, s));
-        break;
-      case ST_GZIP: {
-        GzDirect gd = P.gz;
-        const bool direct = P.gz_direct && si + 1 == P.stages.size() && !P.no_scatter && out &&
-                            ((uintptr_t)out & 15) == 0;
-        gd.dout = direct ? out : nullptr;
-        gd.geom = P.d_geom;
-        // A/B (ZGPU_GZIP_CRC_FORK=1): the trailing crc32c checked on the plan's side stream beside the
-        // one-wave kernel instead of by k_crc32c_strip ahead of it. It loses on C3 (18.11-18.18 ms against
-        // 17.75-17.83 on one box, profiles/r06/r06cf_c3_gzip_crc_fork_ab.txt): the check's workgroups take
-        // CU slots from the latency-bound decode
-        GzCrcFork cf{};
-        const char *fe = std::getenv("ZGPU_GZIP_CRC_FORK");
-        const bool fork = crc_tail == 1 && fe && std::atoi(fe) != 0 && !(P.flags & ZGPU_ONE_STREAM);
-        if (fork) {
-          P.zstd_fork(P.zs, s);  // creates the plan's side stream and events (one compressor per chain)
-        }
-        if (fork && P.zside) {
-          const size_t nb = (size_t)ni * (sizeof(ZgItem) + 8);
-          uint8_t *scr = (uint8_t *)P.grow(P.gz_crc, nb);
-          cf.side = P.zside;
-          cf.ev_fork = P.zev[0];
-          cf.ev_join = P.zev[1];
-          cf.snap_items = (ZgItem *)scr;
-          cf.snap_status = (uint32_t *)(scr + (size_t)ni * sizeof(ZgItem));
-          cf.bad = cf.snap_status + ni;
-        }
-        HIPCHK(launch_gzip(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.slot_bytes, P.d_order, P.d_gz_seg, s,
-                           crc_tail, direct ? &gd : nullptr, cf.side ? &cf : nullptr));
-        wrote_direct = wrote_direct || direct;
-      }
-        crc_tail = 0;
-        break;
-      case ST_ZSTD:
-        P.zstd_fork(P.zs, s);
-        P.zs.lits_first = (P.flags & ZGPU_ZSTD_LITS_FIRST) && !P.zs.side ? 1u : 0u;
-        HIPCHK(launch_zstd(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.slot_bytes, P.zs, s));
-        break;
-      case ST_BLOSC:
-        blosc_stage(P, st, out, s);
-        break;
-      case ST_UNSHUFFLE:
-        HIPCHK(launch_unshuffle(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.slot_bytes, st.elementsize, s));
-        break;
-    }
-    if (!strips_only(st.kind)) len_hint = P.slot_bytes;
-  }
-  if (!P.no_scatter) {
-    // A/B (ZGPU_SCATTER_LIST=1): after the gzip direct rows, the rows scatter over a device-built list
-    // of the items still to write instead of the full grid whose written items' blocks exit at once;
-    // it lost on C3 (18.22-18.33 vs 17.87-17.94 ms, profiles/r06/r06sl_c3_scatter_list_ab.txt)
-    const char *le = std::getenv("ZGPU_SCATTER_LIST");
-    uint32_t *live = nullptr;
-    if (wrote_direct && le && std::atoi(le) != 0)
-      live = (uint32_t *)P.grow(P.live_list, ((size_t)ni + 1) * 4);
-    // both switches are read per launch (tests and A/B runs flip them in one process)
-    const char *pe = std::getenv("ZGPU_TILED_PERSIST");
-    const bool persist = P.tiled_p && (!pe || std::atoi(pe) != 0) && ((uintptr_t)out & 15) == 0;
-    if (persist) {
-      const char *ge = std::getenv("ZGPU_TILED_GRID");
-      const uint32_t cap = ge ? (uint32_t)std::strtoul(ge, nullptr, 10) : 0;
-      HIPCHK(launch_scatter_tiled_p(items, P.d_geom, P.d_status, P.d_origin, P.scatter, P.tiled_q, out, ni, cap, s));
-      P.last_path = ZGPU_SCATTER_TILED_PERSISTENT;
-    } else {
-      HIPCHK(launch_scatter(items, P.d_geom, P.d_status, P.scatter, out, ni, P.scatter_mode, P.scatter_units, s, live));
-      P.last_path = P.scatter_mode;
-    }
-  }
-}
-
-// InvalidBytesLengthError{len, expected_len} of descriptor d's first mismatching leaf item: the item's
-// current {src,len} is the decoded representation the final stage rejected. A materialising stage
-// that overflowed its slot leaves src on its input: the decoded length is then only known to exceed
-// the expected one (len = UINT64_MAX).
-static void size_detail(zgpu_plan &P, uint64_t d, const uint32_t *st, hipStream_t s) {
-  const size_t ni = P.items.size();
-  for (size_t i = 0; i < ni; i++) {
-    if (P.items[i].desc != d || st[i] != ZGPU_DECODED_SIZE_MISMATCH) continue;
-    const bool mutates = P.sharded || !P.stages.empty();
-    ZgItem it{};
-    HIPCHK(hipMemcpyAsync(&it, (mutates ? P.d_items : P.d_items_init) + i, sizeof(ZgItem), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    bool materialised = false, exact = true;
-    for (const Stage &stg : P.stages)
-      if (!strips_only(stg.kind)) materialised = true;
-    if (materialised) {
-      exact = false;
-      for (int k = 0; k < P.n_pools; k++) {
-        const uint64_t lo = (uint64_t)P.d_pool[k], hi = lo + ni * P.slot_bytes;
-        if (it.src >= lo && it.src < hi) exact = true;
-      }
-    }
-    g_size_detail.valid = 1;
-    g_size_detail.desc = d;
-    g_size_detail.len = exact ? it.len : UINT64_MAX;
-    g_size_detail.expected = P.scatter.nelem * P.scatter.es;
-    return;
-  }
-}
-
-// Read back per-item statuses and reduce them to per-descriptor statuses. Returns the first
-// non-zero descriptor status.
-int plan_statuses(zgpu_plan &P, int32_t *status, hipStream_t s) {
-  const size_t ni = P.items.size();
-  HIPCHK(hipMemcpyAsync(P.h_ctl, P.d_ctl, P.ctl_bytes, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (((const uint64_t *)P.h_ctl)[CTR_BLOSC_OVF]) {
-    // the input outgrew the cached blosc layout: nothing was decoded; re-run with a read-back layout
-    P.bl_caps_valid = false;
-    plan_enqueue(P, P.last_out, s);
-    HIPCHK(hipMemcpyAsync(P.h_ctl, P.d_ctl, P.ctl_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    ((uint64_t *)P.h_ctl)[CTR_BLOSC_RERUN] = 1;
-  }
-  if (((const uint64_t *)P.h_ctl)[CTR_ZSTD_SERIAL]) {
-    if (P.zstd_serial_skipped) {
-      // this input has items for the serial zstd decoder, whose launch the plan skipped: re-run with it
-      P.zstd_serial_off = false;
-      plan_enqueue(P, P.last_out, s);
-      HIPCHK(hipMemcpyAsync(P.h_ctl, P.d_ctl, P.ctl_bytes, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-    }
-  } else if (((const uint64_t *)P.h_ctl)[CTR_ZSTD_PARALLEL]) {
-    P.zstd_serial_off = true;  // no serial item: later executions do not launch the fallback
-  }
-  std::memcpy(P.last_counters, P.h_ctl, sizeof(P.last_counters));
-  P.last_counters[CTR_ITEMS] = ni;
-  P.last_counters[CTR_BZ2_ROUNDS] = P.bz_rounds;
-  for (int k = 0; k < CTR_N; k++) g_last_counters[k] += P.last_counters[k];
-  const uint32_t *st = (const uint32_t *)(P.h_ctl + 256);
-  P.last_enc_bytes = P.last_counters[CTR_ENC_BYTES];
-  std::vector<int32_t> ds(P.item_desc_status.begin(), P.item_desc_status.end());
-  for (size_t i = 0; i < ni; i++) {
-    const uint32_t d = P.items[i].desc;
-    if (st[i] && ds[d] == 0) ds[d] = (int32_t)st[i];
-  }
-  int first = 0;
-  uint64_t first_d = 0;
-  for (uint64_t d = 0; d < P.n_desc; d++) {
-    if (status) status[d] = ds[d];
-    if (!first && ds[d]) {
-      first = ds[d];
-      first_d = d;
-    }
-  }
-  if (first == ZGPU_DECODED_SIZE_MISMATCH && !g_size_detail.valid) size_detail(P, first_d, st, s);
-  return first;
-}
-
-zgpu_plan *plan_new(zgpu_ctx *ctx, const std::shared_ptr<Chain> &chain, bool validate, uint32_t nd,
-                           const zgpu_chunk_desc *descs, uint64_t n, const uint64_t *out_shape, uint32_t flags) {
-  auto P = std::make_unique<zgpu_plan>(ctx);
-  P->chain = chain;
-  P->validate = validate && !(flags & ZGPU_NO_VALIDATE);
-  P->nd = nd;
-  P->n_desc = n;
-  P->flags = flags;
-  P->out_shape.assign(out_shape, out_shape + nd);
-  plan_build(*P, descs);
-  return P.release();
-}
-
 static zgpu_plan *plan_new(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *descs, uint64_t n,
                            const uint64_t *out_shape, uint32_t flags) {
   return plan_new(ch->ctx, ch->chain, ch->validate, nd, descs, n, out_shape, flags);
-}
-
-// hip_stream NULL: the context's stream, ordered after all work already queued on the legacy
-// default stream (where torch's default stream and plain hipMemcpy/kernels land), so device buffers a
-// caller produced there are complete before the decode reads or writes them.
-hipStream_t pick_stream(Lane *L, void *s) {
-  if (s) return (hipStream_t)s;
-  if (!L->order_ev) HIPCHK(hipEventCreateWithFlags(&L->order_ev, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(L->order_ev, nullptr));
-  HIPCHK(hipStreamWaitEvent(L->stream, L->order_ev, 0));
-  return L->stream;
-}
-
-// a plan's own stream (executes without a caller stream: an asynchronous execute and its later
-// zgpu_plan_status must meet on one stream)
-static Lane *plan_lane(zgpu_plan &P) {
-  if (!P.own.stream) HIPCHK(hipStreamCreateWithFlags(&P.own.stream, hipStreamNonBlocking));
-  return &P.own;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1160,7 +274,7 @@ void zgpu_plan_destroy(zgpu_plan *P) {
 
 uint32_t zgpu_plan_scatter_path(const zgpu_plan *P) { return P ? P->last_path : ZGPU_SCATTER_GENERIC; }
 
-uint64_t zgpu_plan_algorithmic_bytes(const zgpu_plan *P) { return P ? P->alg_bytes_static + P->last_enc_bytes : 0; }
+uint64_t zgpu_plan_algorithmic_bytes(const zgpu_plan *P) { return P ? P->L.alg_bytes_static + P->last_enc_bytes : 0; }
 
 uint32_t zgpu_plan_counters(const zgpu_plan *P, uint64_t *out, uint32_t n) {
   if (!P || !out) return 0;
