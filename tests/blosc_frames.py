@@ -356,7 +356,9 @@ def _copy(out, off, ml, cap, ip):
         out.append(out[-off])
 
 
-def _lz4(z, cap):
+def _lz4(z, cap, trace=None):
+    """trace (a list): gets ("lit", length, extension bytes) / ("match", length, offset, extension
+    bytes) per element, for tests/encoded_inspect.py; the return value is the same with or without."""
     out, ip, n = bytearray(), 0, len(z)
     while True:
         if ip >= n:
@@ -364,6 +366,7 @@ def _lz4(z, cap):
         tok = z[ip]
         ip += 1
         ll = tok >> 4
+        ip0 = ip
         if ll == 15:
             while True:
                 if ip >= n:
@@ -375,6 +378,8 @@ def _lz4(z, cap):
                     break
         if ip + ll > n or len(out) + ll > cap:
             raise _Bad(ip)
+        if trace is not None and (ll or ip + ll == n):
+            trace.append(("lit", ll, ip - ip0))
         out += z[ip:ip + ll]
         ip += ll
         if ip == n:
@@ -384,6 +389,7 @@ def _lz4(z, cap):
         off = z[ip] | (z[ip + 1] << 8)
         ip += 2
         ml = tok & 15
+        ip0 = ip
         if ml == 15:
             while True:
                 if ip >= n:
@@ -393,12 +399,15 @@ def _lz4(z, cap):
                 ml += b
                 if b != 255:
                     break
+        if trace is not None:
+            trace.append(("match", ml + 4, off, ip - ip0))
         _copy(out, off, ml + 4, cap, ip)
 
 
-def _blosclz(z, cap):
+def _blosclz(z, cap, trace=None):
     """blosclz_decompress of c-blosc 1.21 restated, but a match at the very end of the stream is
-    copied (c-blosc leaves its loop before the copy; only a far match can sit there)."""
+    copied (c-blosc leaves its loop before the copy; only a far match can sit there). trace: as _lz4's,
+    the form of a literal run "run", of a match ("near" | "far", length extension bytes)."""
     out, n = bytearray(), len(z)
     if n == 0:
         raise _Bad(0)
@@ -406,6 +415,7 @@ def _blosclz(z, cap):
     while True:
         if ctrl >= 32:
             ln, ofs = (ctrl >> 5) - 1, (ctrl & 31) << 8
+            ip0, far = ip, False
             if ln == 6:
                 while True:
                     if ip + 1 >= n:
@@ -419,6 +429,7 @@ def _blosclz(z, cap):
                 raise _Bad(ip)
             code = z[ip]
             ip += 1
+            next_ = ip - ip0 - 1
             ln += 3
             dist = ofs + code + 1
             if code == 255 and ofs == 31 << 8:
@@ -426,11 +437,16 @@ def _blosclz(z, cap):
                     raise _Bad(ip)
                 dist = (z[ip] << 8) + z[ip + 1] + 8192
                 ip += 2
+                far = True
+            if trace is not None:
+                trace.append(("match", ln, dist, ("far" if far else "near", next_)))
             _copy(out, dist, ln, cap, ip)
         else:
             run = ctrl + 1
             if len(out) + run > cap or ip + run > n:
                 raise _Bad(ip)
+            if trace is not None:
+                trace.append(("lit", run, "run"))
             out += z[ip:ip + run]
             ip += run
         if ip >= n:
@@ -439,7 +455,9 @@ def _blosclz(z, cap):
         ip += 1
 
 
-def _snappy(z, cap):
+def _snappy(z, cap, trace=None):
+    """trace: as _lz4's, first ("pre", decoded length, preamble bytes); the form of a literal is its
+    length bytes after the tag (0..4), of a copy its tag type (1, 2 or 3)."""
     out, ip, n, want = bytearray(), 0, len(z), 0
     for k in range(6):
         if ip >= n or k == 5:
@@ -451,11 +469,14 @@ def _snappy(z, cap):
             break
     if want > cap or want >= 1 << 32:
         raise _Bad(ip)
+    if trace is not None:
+        trace.append(("pre", want, ip))
     while ip < n:
         tag = z[ip]
         ip += 1
         if tag & 3 == 0:
             ln = (tag >> 2) + 1
+            nb = 0
             if ln > 60:
                 nb = ln - 60
                 if ip + nb > n:
@@ -464,6 +485,8 @@ def _snappy(z, cap):
                 ip += nb
             if ip + ln > n or len(out) + ln > want:
                 raise _Bad(ip)
+            if trace is not None:
+                trace.append(("lit", ln, nb))
             out += z[ip:ip + ln]
             ip += ln
         else:
@@ -476,6 +499,8 @@ def _snappy(z, cap):
             else:
                 ln, off = 1 + (tag >> 2), int.from_bytes(z[ip:ip + nb], "little")
             ip += nb
+            if trace is not None:
+                trace.append(("match", ln, off, form))
             _copy(out, off, ln, want, ip)
     if len(out) != want:
         raise _Bad(ip)

@@ -242,11 +242,23 @@ def huf_stream(lits, lens, codes):
     return w.close_backward()
 
 
+def size_format(n, comp, streams):
+    """Size_Format of a Huffman literals section of n literals in `comp` compressed bytes (tree
+    description, jump table and streams), as k_zstd_encode_seg chooses it: 0 for one stream, else 1 / 2 /
+    3 when both sizes fit 10 / 14 / 18 bits (headers of 3 / 4 / 5 bytes)."""
+    if streams == 1:
+        assert n <= 1023 and comp <= 1023
+        return 0
+    return 1 if (n <= 1023 and comp <= 1023) else 2 if (n <= 16383 and comp <= 16383) else 3
+
+
 def literals_section(lits, table=None):
     """A Compressed_Literals_Block (type 2, with the tree description) or, with table=(lens, codes)
-    from an earlier block, a Treeless_Literals_Block (type 3). Single stream for <= 1023 literals
-    (Size_Format 00), else 4 streams with a 6-byte jump table (Size_Format 01 / 10). Returns
-    (section bytes, (lens, codes)) or (None, None) when Huffman coding does not apply."""
+    from an earlier block, a Treeless_Literals_Block (type 3), of up to 65536 literals. A single stream
+    iff the literal count and the compressed size are both <= 1023 (Size_Format 0), else 4 streams with a
+    6-byte jump table and Size_Format 2 (4-byte header, 14-bit sizes) or 3 (5-byte header, 18-bit
+    sizes): the kernel's rules. Returns (section bytes, (lens, codes)) or (None, None) when Huffman
+    coding does not apply."""
     n = len(lits)
     if table is None:
         freq = np.bincount(np.frombuffer(bytes(lits), np.uint8), minlength=256).tolist()
@@ -261,22 +273,26 @@ def literals_section(lits, table=None):
     else:
         lens, codes = table
         desc, ltype = b"", 3
-    if n <= 1023:
-        streams = huf_stream(lits, lens, codes)
-        comp = desc + streams
-        if len(comp) > 1023:
-            return None, None
-        hdr = ltype | (0 << 2) | (n << 4) | (len(comp) << 14)
-        return hdr.to_bytes(3, "little") + comp, (lens, codes)
+    if n > 65536:
+        raise ValueError("a block holds at most 65536 literals here (the kernel's block size)")
+    # the kernel's selection (k_zstd_encode_seg): one stream iff both the literal count and the
+    # compressed size fit 10 bits; else 4 streams, whose header is Size_Format 1 / 2 / 3 by 10 / 14 /
+    # 18-bit sizes (1 cannot occur: 4 streams are only chosen when a 10-bit field is too small)
+    one = desc + huf_stream(lits, lens, codes)
+    if n <= 1023 and len(one) <= 1023:
+        hdr = ltype | (0 << 2) | (n << 4) | (len(one) << 14)
+        return hdr.to_bytes(3, "little") + one, (lens, codes)
     seg = (n + 3) // 4
-    parts = [huf_stream(lits[i * seg:min(n, (i + 1) * seg)], lens, codes) for i in range(4)]
+    parts = [huf_stream(lits[min(n, i * seg):min(n, (i + 1) * seg)], lens, codes) for i in range(4)]
     jump = b"".join(len(p).to_bytes(2, "little") for p in parts[:3])
     comp = desc + jump + b"".join(parts)
-    if n <= 1023 and len(comp) <= 1023:
-        hdr = ltype | (1 << 2) | (n << 4) | (len(comp) << 14)
-        return hdr.to_bytes(3, "little") + comp, (lens, codes)
-    hdr = ltype | (2 << 2) | (n << 4) | (len(comp) << 18)
-    return hdr.to_bytes(4, "little") + comp, (lens, codes)
+    sf = size_format(n, len(comp), 4)
+    if sf == 2:
+        hdr = ltype | (2 << 2) | (n << 4) | (len(comp) << 18)
+        return hdr.to_bytes(4, "little") + comp, (lens, codes)
+    assert sf == 3 and n < 1 << 18 and len(comp) < 1 << 18
+    hdr = ltype | (3 << 2) | (n << 4) | (len(comp) << 22)
+    return hdr.to_bytes(5, "little") + comp, (lens, codes)
 
 
 def frame_of_literal_blocks(data, block=4096, treeless=True):
