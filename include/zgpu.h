@@ -29,6 +29,11 @@
  *   zgpu_encode_chunks  <- the same for variable-length chains: GzipCodec::encode (gzip_codec.rs:
  *                          96-107), ZstdCodec::encode (zstd_codec.rs:100-111), crc32c around them, and
  *                          ShardingCodecBound::encode_bounded (sharding_codec.rs:924-1085)
+ *   zgpu_store_array_subset
+ *                       <- Array::store_array_subset: store_chunk_with_options (zarrs/src/array/array_ops/
+ *                          array_write_ops_array.rs:183-208), store_chunk_subset_with_options
+ *                          (array_update_ops_array.rs:152-210) and, inside a shard, the inner-chunk
+ *                          update of sharding/sharding_partial_encoder.rs
  *   status codes        <- CodecError variants (zarrs_codec/src/lib.rs:617-686), 1:1 (see below).
  *
  * Threading: every entry point is thread-safe. Calls on one context run concurrently: each takes one
@@ -336,7 +341,12 @@ void zgpu_group_destroy(zgpu_group *group);
 #define ZGPU_CTR_BZ2_ROUNDS 8    /* rounds the numcodecs.bz2 stage ran: 1 per execution whose scratch fits
                                     ZGPU_BZ2_SCRATCH_MB, more when the batch is cut; a whole-shard bz2
                                     stage adds the rounds of every run of its slot regrowing           */
-#define ZGPU_N_COUNTERS 9
+#define ZGPU_CTR_STORE_DECODED 9 /* zgpu_store_array_subset: partly covered leaf chunks (chunks, or inner chunks
+                                    of shards) whose old bytes were decoded for the read-modify-write    */
+#define ZGPU_CTR_STORE_ENCODED 10 /* zgpu_store_array_subset: leaf chunks encoded                          */
+#define ZGPU_CTR_STORE_CARRIED 11 /* zgpu_store_array_subset: untouched inner chunks whose encoded bytes were
+                                    copied from the old shard into the new one                           */
+#define ZGPU_N_COUNTERS 12
 uint32_t zgpu_plan_counters(const zgpu_plan *plan, uint64_t *out, uint32_t n);
 uint32_t zgpu_last_counters(uint64_t *out, uint32_t n);
 
@@ -463,6 +473,74 @@ int zgpu_encode_pinned(zgpu_chain *chain, uint32_t ndim, const uint64_t *chunk_s
 int zgpu_encode_chunks(zgpu_chain *chain, uint32_t ndim, const uint64_t *chunk_shape, const void *array,
                        const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint32_t flags,
                        uint64_t *enc_lens, void *hip_stream);
+
+/*
+ * Array::store_array_subset over a regular chunk grid (zarrs/src/array/array_ops/
+ * array_write_ops_array.rs:183-208, store_chunk_with_options; array_update_ops_array.rs:152-210,
+ * store_chunk_subset_with_options; for sharded arrays the inner-chunk update of
+ * sharding/sharding_partial_encoder.rs). The subset [sel_start, sel_start + sel_shape) of the array takes
+ * the values of `data` (C order, native-endian elements). The unit of read-modify-write is the leaf
+ * chunk: the chunk, or for a sharding_indexed chain (one level, nothing around it, index = bytes +
+ * crc32c codecs) the inner chunk. For every leaf chunk of every chunk the subset meets:
+ *   covered (its whole box lies inside the subset): encoded from `data`; the old bytes are not read;
+ *   partly covered: the old leaf chunk is decoded in full (checksums verified; missing = fill value),
+ *     the overlap pasted in (k_subset_overlay) and the result encoded; elements past the array's edge
+ *     keep what the old chunk decoded to;
+ *   untouched (inner chunks only): neither decoded nor encoded; its encoded bytes are copied from the
+ *     old shard as its index gives them (not checksum-verified), an absent one stays absent.
+ * A leaf chunk whose new content equals the fill value bytewise in every element is not written
+ * (store_empty_chunks = false, array_write_ops_array.rs:192-199): the chunk is erased, the inner chunk
+ * omitted from its shard. ZGPU_STORE_EMPTY_CHUNKS stores such chunks (inner chunks are omitted all the
+ * same, as the sharding codec omits them). A shard left without an inner chunk is erased. New shards
+ * are laid out as zgpu_encode_chunks lays them out.
+ * chunk_ptrs / chunk_lens: the old encoded chunks as for zgpu_retrieve_array_subset; only chunks that
+ * the subset meets without covering are read (zgpu_store_classify tells which).
+ * flags: ZGPU_ENC_DEVICE: the old chunks are device memory and every entry's enc is device memory;
+ * otherwise host memory in, pooled pinned host memory out. ZGPU_OUT_DEVICE: `data` is device memory.
+ * ZGPU_NO_VALIDATE as for decoding. *entries: one entry per chunk the subset meets, in C order of the
+ * chunk grid, valid with their enc until zgpu_result_release(*result). An entry whose old bytes failed
+ * to decode (or whose old shard index is corrupt: ZGPU_INVALID_CHECKSUM, or points outside the shard:
+ * ZGPU_SHARD_INDEX_OOB, checked for every entry, those of untouched inner chunks included) carries that
+ * status and no action; the other entries are valid. Returns the first non-zero entry status, or a
+ * call-level error (*entries NULL): ZGPU_UNSUPPORTED, before any GPU work, for a chain
+ * zgpu_encode_chunks refuses, for codecs around sharding_indexed, nested sharding, or value codecs or
+ * packbits with sharding; ZGPU_INVALID_ARGUMENT for a subset outside the array. A zero-volume subset is
+ * ZGPU_OK with no entries and no result. Synchronous on hip_stream. No locking (zarrs' is commented
+ * out): the caller serialises writers of one chunk.
+ */
+#define ZGPU_STORE_EMPTY_CHUNKS 0x80u
+#define ZGPU_STORE_SET 1
+#define ZGPU_STORE_ERASE 2
+typedef struct {
+  uint64_t chunk;   /* C-order linear chunk-grid index */
+  uint32_t action;  /* ZGPU_STORE_SET / ZGPU_STORE_ERASE; 0 when status != 0 */
+  int32_t status;
+  const void *enc;  /* ZGPU_STORE_SET: the chunk's new encoded bytes */
+  uint64_t enc_len;
+} zgpu_store_entry;
+int zgpu_store_array_subset(zgpu_chain *chain, uint32_t ndim, const uint64_t *array_shape,
+                            const uint64_t *chunk_shape, const void *const *chunk_ptrs, const uint64_t *chunk_lens,
+                            const uint64_t *sel_start, const uint64_t *sel_shape, const void *data, uint32_t flags,
+                            const zgpu_store_entry **entries, uint64_t *n_entries, zgpu_result **result,
+                            void *hip_stream);
+/* One ZGPU_STORE_SET entry's encoded bytes copied to dst (enc_len bytes; host or device memory,
+ * whichever side enc is on) before the result is released: for stores that keep buffers of their own.
+ * Synchronous on hip_stream. */
+int zgpu_store_entry_copy(zgpu_chain *chain, const zgpu_store_entry *entry, void *dst, void *hip_stream);
+/*
+ * The host's classification behind zgpu_store_array_subset, without a device: the chunks the subset
+ * meets in C order of the chunk grid (chunks[k]: linear index) and, per chunk, the class of each of its
+ * leaf chunks in C order of the inner grid (leaf_class[k * leaves_per_chunk + j]; leaf_shape NULL or
+ * equal to chunk_shape: one leaf per chunk). *n_chunks receives the number of chunks met; entries are
+ * written only while they fit cap (call with cap 0 to size the arrays). A chunk must be fetched from
+ * the store unless every leaf of it is ZGPU_LEAF_COVERED.
+ */
+#define ZGPU_LEAF_UNTOUCHED 0
+#define ZGPU_LEAF_PARTIAL 1
+#define ZGPU_LEAF_COVERED 2
+int zgpu_store_classify(uint32_t ndim, const uint64_t *array_shape, const uint64_t *chunk_shape,
+                        const uint64_t *leaf_shape, const uint64_t *sel_start, const uint64_t *sel_shape,
+                        uint64_t *chunks, uint8_t *leaf_class, uint64_t cap, uint64_t *n_chunks);
 
 /*
  * HBM-resident decoded-chunk cache: ChunkCacheDecodedLruSizeLimit (zarrs/src/array/chunk_cache/

@@ -45,11 +45,16 @@ EXPORTS = [
     "zgpu_encode_pinned", "zgpu_ctx_release_cached", "zgpu_ctx_pool_stats",
     "zgpu_group_create", "zgpu_group_execute", "zgpu_group_status", "zgpu_group_layout",
     "zgpu_group_algorithmic_bytes", "zgpu_group_counters", "zgpu_group_destroy", "zgpu_plan_scatter_path",
+    "zgpu_store_array_subset", "zgpu_store_entry_copy", "zgpu_store_classify",
 ]
 SCATTER_ROWS, SCATTER_TILED, SCATTER_GENERIC, SCATTER_TILED_PERSISTENT = range(4)  # zgpu_plan_scatter_path
 CTR_ENC_BYTES, CTR_ZSTD_SERIAL, CTR_ZSTD_PARALLEL, CTR_BLOSC_RERUN, CTR_BLOSC_BLOCKS, CTR_ITEMS, \
-    CTR_ZSTD_LATENCY, CTR_BZ2_BLOCKS, CTR_BZ2_ROUNDS = range(9)
-N_COUNTERS = 9
+    CTR_ZSTD_LATENCY, CTR_BZ2_BLOCKS, CTR_BZ2_ROUNDS, CTR_STORE_DECODED, CTR_STORE_ENCODED, \
+    CTR_STORE_CARRIED = range(12)
+N_COUNTERS = 12
+STORE_EMPTY_CHUNKS = 0x80  # zgpu_store_array_subset flag
+STORE_SET, STORE_ERASE = 1, 2  # zgpu_store_entry.action
+LEAF_UNTOUCHED, LEAF_PARTIAL, LEAF_COVERED = range(3)  # zgpu_store_classify
 
 
 class ChunkDesc(C.Structure):
@@ -79,6 +84,12 @@ class FileRange(C.Structure):
 
 class EncodeDesc(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("dst_cap", C.c_uint64), ("chunk_start", C.c_uint64 * MAX_DIMS)]
+
+
+class StoreEntry(C.Structure):
+    """zgpu_store_entry: what one chunk of a store becomes."""
+    _fields_ = [("chunk", C.c_uint64), ("action", C.c_uint32), ("status", C.c_int32), ("enc", C.c_void_p),
+                ("enc_len", C.c_uint64)]
 
 
 class DLDevice(C.Structure):
@@ -197,6 +208,10 @@ def load() -> C.CDLL:
     L.zgpu_cache_retrieve_array_subset.argtypes = [vp, vp, u32, P64, P64, C.POINTER(vp), P64, P64, P64, vp, u32, vp]
     L.zgpu_retrieve_array_subset_dlpack.argtypes = [vp, vp, u32, P64, P64, C.POINTER(vp), P64, P64, P64, u32, vp,
                                                     C.POINTER(C.POINTER(DLManagedTensor))]
+    L.zgpu_store_array_subset.argtypes = [vp, u32, P64, P64, C.POINTER(vp), P64, P64, P64, vp, u32,
+                                          C.POINTER(C.POINTER(StoreEntry)), P64, C.POINTER(vp), vp]
+    L.zgpu_store_entry_copy.argtypes = [vp, C.POINTER(StoreEntry), vp, vp]
+    L.zgpu_store_classify.argtypes = [u32, P64, P64, P64, P64, P64, P64, C.POINTER(C.c_uint8), u64, P64]
     _lib = L
     return L
 
@@ -210,7 +225,25 @@ def last_counters() -> dict:
     buf = (C.c_uint64 * N_COUNTERS)()
     load().zgpu_last_counters(buf, N_COUNTERS)
     return {"enc_bytes": buf[0], "zstd_serial": buf[1], "zstd_parallel": buf[2], "blosc_rerun": buf[3],
-            "blosc_blocks": buf[4], "zstd_latency": buf[6], "bz2_blocks": buf[7], "bz2_rounds": buf[8]}
+            "blosc_blocks": buf[4], "zstd_latency": buf[6], "bz2_blocks": buf[7], "bz2_rounds": buf[8],
+            "store_decoded": buf[9], "store_encoded": buf[10], "store_carried": buf[11]}
+
+
+def store_classify(array_shape, chunk_shape, leaf_shape, start, shape):
+    """zgpu_store_classify: [(linear chunk index, [class of each leaf chunk])] of the chunks the subset
+    meets, in C order of the chunk grid (no device involved)."""
+    nd = len(array_shape)
+    args = (nd, u64s(array_shape), u64s(chunk_shape), u64s(leaf_shape) if leaf_shape is not None else None,
+            u64s(start), u64s(shape))
+    n = C.c_uint64()
+    check(load().zgpu_store_classify(*args, None, None, 0, C.byref(n)))
+    lpc = 1
+    for c, l in zip(chunk_shape, leaf_shape if leaf_shape is not None else chunk_shape):
+        lpc *= int(c) // int(l)
+    chunks = (C.c_uint64 * max(n.value, 1))()
+    cls = (C.c_uint8 * max(n.value * lpc, 1))()
+    check(load().zgpu_store_classify(*args, chunks, cls, n.value, C.byref(n)))
+    return [(int(chunks[k]), list(cls[k * lpc:(k + 1) * lpc])) for k in range(n.value)]
 
 
 def last_size_mismatch():

@@ -26,12 +26,21 @@ from . import _lib as L
 from .codec import CodecChain, Context, default_stream
 
 
-class MemoryStore(dict):
+class _DictStore(dict):
+    def set(self, key, value) -> None:
+        self[key] = value
+
+    def erase(self, key) -> None:
+        """Remove a key; a missing key is not an error (WritableStorageTraits::erase)."""
+        self.pop(key, None)
+
+
+class MemoryStore(_DictStore):
     """key -> encoded bytes (host memory)."""
     device = False
 
 
-class DeviceStore(dict):
+class DeviceStore(_DictStore):
     """key -> torch.uint8 device tensor (HBM-resident encoded bytes)."""
     device = True
 
@@ -84,6 +93,14 @@ class FilesystemStore:
             f.write(value)
 
     __setitem__ = set
+
+    def erase(self, key: str) -> None:
+        """Remove a key's file; a missing key is not an error (zarrs_filesystem/src/lib.rs erase)."""
+        import os
+        try:
+            os.remove(self.key_to_fspath(key))
+        except (FileNotFoundError, NotADirectoryError):
+            pass
 
     def decode_files(self, chain, descs, ranges, out, out_shape, status=None):
         """zgpu_decode_files: descs (ChunkDesc array) with their (key, offset, length) ranges
@@ -152,10 +169,11 @@ class Array:
     def chunk_grid_shape(self):
         return [-(-s // c) for s, c in zip(self.shape, self.chunk_shape)]
 
-    def _tables(self, start, shape):
+    def _tables(self, start, shape, skip_covered=False):
         """Pointer tables indexed by the C-order linear chunk-grid index; only the chunks the subset
         intersects are looked up in the store (chunks_in_array_subset, array_ops_array.rs:341-346),
-        the others stay NULL. Host bytes are passed zero-copy."""
+        the others stay NULL. Host bytes are passed zero-copy. skip_covered (the store path): chunks
+        whose whole box lies inside the subset are not looked up either."""
         grid = self.chunk_grid_shape()
         n = int(np.prod(grid))
         ptrs = (C.c_void_p * n)()
@@ -166,6 +184,9 @@ class Array:
         ranges = [range(int(st) // c, (int(st) + int(sh) - 1) // c + 1)
                   for st, sh, c in zip(start, shape, self.chunk_shape)]
         for idx in itertools.product(*ranges):
+            if skip_covered and all(int(st) <= i * c and (i + 1) * c <= int(st) + int(sh)
+                                    for i, c, st, sh in zip(idx, self.chunk_shape, start, shape)):
+                continue
             v = self.store.get(self.chunk_key(idx))
             if v is None:
                 continue
@@ -325,6 +346,66 @@ class Array:
         start = [int(i) * c for i, c in zip(idx, self.chunk_shape)]
         shape = [min(c, s - st) for c, s, st in zip(self.chunk_shape, self.shape, start)]
         return self.retrieve_array_subset(start, shape)
+
+    # ---- write path ------------------------------------------------------------------------
+    def store_array_subset(self, start, data, store_empty_chunks: bool = False) -> list:
+        """Array::store_array_subset (array_write_ops_array.rs:183-208, array_update_ops_array.rs:
+        152-210; inner chunks of a shard as sharding_partial_encoder.rs) by zgpu_store_array_subset:
+        the subset at `start` takes `data` (numpy array or torch tensor, host or device, of the
+        subset's shape). Only the chunks the subset meets without covering are read from the store.
+        The store is changed only if every chunk succeeded: otherwise ZgpuError is raised with the
+        first failing chunk's status and the store is untouched. A chunk whose new content is the
+        fill value everywhere is erased unless store_empty_chunks. No locking: the caller serialises
+        writers of one chunk, and clears an ArrayCached's cache after a store.
+        Returns [(chunk key, L.STORE_SET or L.STORE_ERASE)] in chunk-grid order."""
+        if not hasattr(data, "shape"):
+            data = np.asarray(data)
+        if isinstance(data, np.ndarray):
+            data = np.ascontiguousarray(data, dtype=None if self.dtype.kind == "V" else self.dtype)
+        else:
+            data = data.contiguous()
+        start = [int(v) for v in start]
+        shape = [int(v) for v in data.shape]
+        if len(start) != self.ndim or len(shape) != self.ndim:
+            raise L.ZgpuError(L.INVALID_ARGUMENT, "store: subset rank != array rank")
+        if any(st < 0 or st + sh > s for st, sh, s in zip(start, shape, self.shape)):
+            raise L.ZgpuError(L.INVALID_ARGUMENT, "array subset out of bounds")
+        if isinstance(self.store, FilesystemStore) and getattr(data, "is_cuda", False):
+            data = data.cpu()  # host chunks in, host chunks out
+        ptrs, lens, keep = self._tables(start, shape, skip_covered=True)
+        res = self.codecs.store_array_subset(self.shape, self.chunk_shape, ptrs, lens, start, data,
+                                             bool(self.store.device), store_empty_chunks)
+        del keep
+        try:
+            if res.rc:
+                raise L.ZgpuError(res.rc, L.last_error())
+            grid = self.chunk_grid_shape()
+            done = []
+            new = [res.encoded(i) if action == L.STORE_SET else None
+                   for i, (_, action, _, _, _) in enumerate(res.entries)]
+            for (lin, action, _, _, _), v in zip(res.entries, new):
+                key = self.chunk_key(np.unravel_index(lin, grid))
+                if action == L.STORE_SET:
+                    self.store.set(key, v)
+                else:
+                    self.store.erase(key)
+                done.append((key, action))
+            return done
+        finally:
+            res.release()
+
+    def store_chunk(self, idx, data) -> list:
+        """Array::store_chunk (array_write_ops_array.rs:183-208): chunk `idx` takes `data`, whose shape
+        is the part of the chunk inside the array (retrieve_chunk's shape)."""
+        start = [int(i) * c for i, c in zip(idx, self.chunk_shape)]
+        shape = [min(c, s - st) for c, s, st in zip(self.chunk_shape, self.shape, start)]
+        if [int(v) for v in data.shape] != shape:
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"store_chunk: data of shape {list(data.shape)}, chunk of {shape}")
+        return self.store_array_subset(start, data)
+
+    def erase_chunk(self, idx) -> None:
+        """Array::erase_chunk: the chunk's key removed from the store (it then reads as fill value)."""
+        self.store.erase(self.chunk_key(idx))
 
 
 class ChunkCacheDecodedLruSizeLimit:

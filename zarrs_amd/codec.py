@@ -311,12 +311,71 @@ class CodecChain:
         L.check(rc)
         return [flat[i * pitch:i * pitch + lens[i]] for i in range(n)]
 
+    def store_array_subset(self, array_shape, chunk_shape, ptrs, lens, start, data, enc_device: bool,
+                           store_empty_chunks: bool = False, stream=None) -> "StoreResult":
+        """zgpu_store_array_subset: the subset at `start` of an array of `array_shape` takes `data`
+        (numpy array or torch tensor, host or device; its shape is the subset's). ptrs / lens: the old
+        encoded chunks by linear chunk-grid index (Array._tables). Returns the entries (one per chunk
+        the subset meets) in a StoreResult that owns their encoded bytes until release(); a call-level
+        error raises ZgpuError, a failing entry does not (StoreResult.rc is its status)."""
+        dp, nbytes, ddev, keep = _ptr_len(data)
+        shape = [int(v) for v in data.shape]
+        if nbytes != int(np.prod(shape)) * self.dtype.itemsize:
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"store: {data.dtype} data for a {self.data_type} chain")
+        if len(shape) != len(array_shape):
+            raise L.ZgpuError(L.INVALID_ARGUMENT, "store: data rank != array rank")
+        flags = (L.ENC_DEVICE if enc_device else 0) | (L.OUT_DEVICE if ddev else 0) | \
+            (L.STORE_EMPTY_CHUNKS if store_empty_chunks else 0)
+        ents, n, res = C.POINTER(L.StoreEntry)(), C.c_uint64(), C.c_void_p()
+        rc = L.load().zgpu_store_array_subset(
+            self._h, len(array_shape), L.u64s(array_shape), L.u64s(chunk_shape), ptrs, lens, L.u64s(start),
+            L.u64s(shape), dp, flags, C.byref(ents), C.byref(n), C.byref(res), default_stream(stream, data))
+        del keep
+        if rc and not res:
+            raise L.ZgpuError(rc, L.last_error())
+        return StoreResult(self, rc, ents, n.value, res, enc_device)
+
     def partial_decode(self, encoded, shape, subset_start, subset_shape) -> np.ndarray:
         out = np.empty([int(s) for s in subset_shape], dtype=self.dtype)
         dev = _ptr_len(encoded)[2]
         self.decode_batch([make_desc(encoded, shape, subset_start, subset_shape)], out,
                           list(subset_shape), dev)
         return out
+
+
+class StoreResult:
+    """The entries of one zgpu_store_array_subset call and the zgpu_result that owns their encoded
+    bytes. entries: (chunk, action, status, enc, enc_len) per chunk met, in chunk-grid order."""
+
+    def __init__(self, chain, rc, ents, n, res, device):
+        self.chain, self.rc, self._res, self.device = chain, rc, res, device
+        self._ents = ents
+        self.entries = [(ents[i].chunk, ents[i].action, ents[i].status, ents[i].enc, ents[i].enc_len)
+                        for i in range(n)]
+
+    def encoded(self, i, stream=None):
+        """Entry i's encoded bytes, copied out of the result: bytes, or for a device result a
+        torch.uint8 device tensor."""
+        _, action, _, enc, n = self.entries[i]
+        assert action == L.STORE_SET and self._res
+        if not self.device:
+            return C.string_at(enc, n) if n else b""
+        import torch
+        t = torch.empty(n, dtype=torch.uint8, device=f"cuda:{self.chain.ctx.device}")
+        L.check(L.load().zgpu_store_entry_copy(self.chain._h, C.byref(self._ents[i]), t.data_ptr() if n else None,
+                                               default_stream(stream, t)))
+        return t
+
+    def release(self):
+        if self._res:
+            L.load().zgpu_result_release(self._res)
+            self._res = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 class PlanGroup:

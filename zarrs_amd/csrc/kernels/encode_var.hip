@@ -180,6 +180,15 @@ hipError_t launch_shard_encode_var(const uint64_t *starts, const uint8_t *array,
   if (!n_chunks) return hipSuccess;
   hipError_t e = launch_fill_check(starts, array, inner, n_chunks, nonfill, s);
   if (e != hipSuccess) return e;
+  return launch_shard_layout_var(n_chunks, nonfill, items, item_status, A, shard_dst, inner_off, index_ptr, shard_len,
+                                 shard_status, n_shards, s);
+}
+
+hipError_t launch_shard_layout_var(uint32_t n_chunks, const uint32_t *nonfill, const ZgItem *items,
+                                   const uint32_t *item_status, const ZgShardLayoutArgs &A, const uint64_t *shard_dst,
+                                   uint64_t *inner_off, uint64_t *index_ptr, uint64_t *shard_len,
+                                   uint32_t *shard_status, uint32_t n_shards, hipStream_t s) {
+  if (!n_chunks) return hipSuccess;
   hipLaunchKernelGGL(k_shard_layout_var, dim3(n_shards), dim3(256), 0, s, nonfill, items, item_status, A, shard_dst,
                      inner_off, index_ptr, shard_len, shard_status);
   hipLaunchKernelGGL(k_shard_copy_var, dim3(n_chunks), dim3(256), 0, s, items, A.n_inner, shard_dst, inner_off);

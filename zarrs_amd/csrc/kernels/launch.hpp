@@ -255,6 +255,24 @@ hipError_t launch_shard_encode_var(const uint64_t *starts, const uint8_t *array,
                                    const uint32_t *item_status, const ZgShardLayoutArgs &A, const uint64_t *shard_dst,
                                    uint64_t *inner_off, uint64_t *index_ptr, uint64_t *shard_len,
                                    uint32_t *shard_status, uint32_t n_shards, hipStream_t s);
+// launch_shard_encode_var after its fill check: the layout and the copies over items and nonfill flags
+// the caller made (the store path: an untouched inner chunk's item points into the old shard)
+hipError_t launch_shard_layout_var(uint32_t n_chunks, const uint32_t *nonfill, const ZgItem *items,
+                                   const uint32_t *item_status, const ZgShardLayoutArgs &A, const uint64_t *shard_dst,
+                                   uint64_t *inner_off, uint64_t *index_ptr, uint64_t *shard_len,
+                                   uint32_t *shard_status, uint32_t n_shards, hipStream_t s);
+
+// ---- store path (kernels/store.hip) ----
+// One overlap box of a read-modify-write: ext elements (nd axes) from src (the stored subset) to dst
+// (the leaf chunk's staging box); strides in elements, the innermost of both is 1. src and dst are
+// aligned to min(es, 8).
+struct ZgOverlayBox {
+  uint64_t src, dst;
+  uint64_t ext[ZG_MAXD], src_stride[ZG_MAXD], dst_stride[ZG_MAXD];
+};
+// rows: n_boxes + 1 prefix sums of the boxes' innermost runs (rows[n_boxes] == n_rows), on the device
+hipError_t launch_subset_overlay(const ZgOverlayBox *boxes, const uint64_t *rows, uint32_t n_boxes, uint64_t n_rows,
+                                 uint32_t nd, uint32_t es, hipStream_t s);
 
 // The value codecs and packbits (kernels/value.hip). vt_*: ZgValueType of the encoded / decoded
 // elements, VT_I8..VT_F64; through_f32: `astype` was given, so the cast between the two types runs (through

@@ -191,8 +191,11 @@ struct zgpu_result {
   zgpu_ctx *ctx = nullptr;
   uint8_t *own = nullptr;             // pooled pinned buffer (uncoalesced call)
   std::shared_ptr<CoBatch> batch;     // coalesced call: the batch holding the pack
+  uint8_t *dev = nullptr;             // pooled device buffer (zgpu_store_array_subset with ZGPU_ENC_DEVICE)
+  std::vector<zgpu_store_entry> store_entries;  // zgpu_store_array_subset's entries (enc inside own / dev)
   ~zgpu_result() {
     if (own) ctx->host_free(own);
+    if (dev) ctx->dev_free(dev);
     batch.reset();
     ctx_unref(ctx);
   }
@@ -219,4 +222,8 @@ std::shared_ptr<Chain> strip_value_codecs(const Chain &c, std::vector<Codec> &st
 void retype_stripped(Chain &c, const Chain &original);
 uint8_t *value_encode_elements(const std::vector<Codec> &steps, const uint8_t *in, uint64_t n, Scratch &sc,
                                hipStream_t s);
+// write.cpp: zgpu_encode_chunks (arguments checked) on stream s, synchronous
+int encode_chunks_on(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, const void *array,
+                     const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint64_t *enc_lens,
+                     hipStream_t s);
 #pragma GCC visibility pop

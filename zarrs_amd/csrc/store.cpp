@@ -1,0 +1,577 @@
+// libzgpu: the store path -- Array::store_array_subset on the GPU (zgpu_store_array_subset, zgpu.h).
+//
+// zarrs stores a subset chunk by chunk (array_write_ops_array.rs:183-208 for a covered chunk,
+// array_update_ops_array.rs:152-210 for a partly covered one: decode, paste, encode) and, in a shard,
+// inner chunk by inner chunk (sharding/sharding_partial_encoder.rs). Here the unit of read-modify-write
+// is the leaf chunk throughout, and one call does every chunk the subset meets:
+//   1. store_classify (store_layout.cpp, no device): the chunks met, each leaf covered / partly
+//      covered / untouched;
+//   2. the old shard indexes (small) are decoded on the host: every entry is range-checked here, so an
+//      untouched inner chunk is never copied from outside its shard;
+//   3. ONE decode batch of all partly covered leaves (decode_general over the leaf chain, full decode
+//      path, checksums verified) into a staging array of one leaf box per leaf, stacked along axis 0;
+//   4. ONE k_subset_overlay launch pastes every overlap box from the data into its staging box;
+//   5. k_fill_check of the staged and of the covered leaves (the latter straight in the data);
+//   6. the leaves that are not all fill go through the write path's encoder (encode_chunks_on):
+//      the staged ones with the staging array as the array, the covered ones straight from the data
+//      (array_shape = sel_shape, origins relative to sel_start);
+//   7. a shard is laid out by k_shard_layout_var / k_shard_copy_var over one item per inner chunk: the
+//      newly encoded ones, and the untouched ones pointing into the old shard; then the index crc32c.
+// Every temporary is Scratch's; the encoded chunks leave in the result (pooled pinned or device memory).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/zgpu.h"
+#include "chain.hpp"
+#include "common.hpp"
+#include "ctx.hpp"
+#include "kernels/launch.hpp"
+#include "plan.hpp"
+#include "store_layout.hpp"
+
+using namespace zgpu;
+
+namespace {
+
+// CRC-32C (Castagnoli, reflected polynomial 0x82F63B78) of the few bytes of a shard index
+uint32_t crc32c_host(const uint8_t *p, size_t n) {
+  static const std::vector<uint32_t> T = [] {
+    std::vector<uint32_t> t(256);
+    for (uint32_t i = 0; i < 256; i++) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1)));
+      t[i] = c;
+    }
+    return t;
+  }();
+  uint32_t c = ~0u;
+  for (size_t i = 0; i < n; i++) c = T[(c ^ p[i]) & 0xFF] ^ (c >> 8);
+  return ~c;
+}
+
+uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
+
+// What encode_fixed / encode_var / encode_packbits (write.cpp) take, checked without the device.
+int leaf_chain_check(const Chain &c, uint32_t nd, bool packbits_ok) {
+  if (c.a2b.kind == CodecKind::PackBits ? !packbits_ok : c.a2b.kind != CodecKind::Bytes)
+    return set_err(ZGPU_UNSUPPORTED, "store: array->bytes codec must be bytes (or packbits, unsharded)");
+  for (const Codec &k : c.a2a)
+    if (k.kind == CodecKind::Transpose && k.order.size() != nd)
+      return set_err(ZGPU_INVALID_ARGUMENT, "transpose order rank != ndim");
+  const uint32_t es = c.a2b.kind == CodecKind::PackBits ? 1 : c.enc_es;
+  bool var_len = false;
+  for (size_t i = 0; i < c.b2b.size(); i++) {
+    const Codec &k = c.b2b[i];
+    if (k.kind == CodecKind::Shuffle && i == 0 && k.elementsize == es) continue;
+    if (is_checksum(k.kind)) continue;
+    if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib || k.kind == CodecKind::Zstd) {
+      var_len = true;
+      continue;
+    }
+    if (k.kind == CodecKind::Blosc && !var_len &&
+        (k.cname == "lz4" || k.cname == "lz4hc" || k.cname == "zstd" || k.cname == "blosclz" || k.cname == "zlib" ||
+         k.cname == "snappy")) {
+      var_len = true;
+      continue;
+    }
+    if (k.kind == CodecKind::Bz2) return set_err(ZGPU_UNSUPPORTED, "store: numcodecs.bz2 is decode-only on the GPU");
+    return set_err(ZGPU_UNSUPPORTED, "store: the chain has a codec the GPU write path does not encode");
+  }
+  return ZGPU_OK;
+}
+
+int store_chain_check(const Chain &top, uint32_t nd, const uint64_t *chunk_shape) {
+  if (top.a2b.kind != CodecKind::Sharding) return leaf_chain_check(top, nd, true);
+  if (!top.a2a.empty() || !top.b2b.empty()) return set_err(ZGPU_UNSUPPORTED, "store: codecs around sharding_indexed");
+  const Chain &inner = *top.a2b.inner, &xc = *top.a2b.index;
+  if (inner.a2b.kind == CodecKind::Sharding) return set_err(ZGPU_UNSUPPORTED, "store: nested sharding_indexed");
+  if (chain_has_value_codec(inner)) return set_err(ZGPU_UNSUPPORTED, "store: value codecs inside sharding_indexed");
+  if (xc.a2b.kind != CodecKind::Bytes || !xc.a2a.empty())
+    return set_err(ZGPU_UNSUPPORTED, "index_codecs must be bytes (+crc32c)");
+  for (const Codec &k : xc.b2b)
+    if (k.kind != CodecKind::Crc32c) return set_err(ZGPU_UNSUPPORTED, "index_codecs must be bytes (+crc32c)");
+  if (top.a2b.inner_shape.size() != nd) return set_err(ZGPU_INVALID_ARGUMENT, "sharding chunk_shape rank");
+  for (uint32_t d = 0; d < nd; d++)
+    if (!top.a2b.inner_shape[d] || chunk_shape[d] % top.a2b.inner_shape[d])
+      return set_err(ZGPU_INVALID_ARGUMENT, "shard shape not a multiple of chunk_shape");
+  return leaf_chain_check(inner, nd, false);
+}
+
+// An encoded shard index (X bytes: bytes{endian} + crc32c codecs) decoded on the host into n_inner
+// (offset, nbytes) pairs, every present entry checked against the shard's length.
+int parse_index(const uint8_t *enc, uint64_t X, const Chain &xc, uint64_t n_inner, bool validate, uint64_t shard_len,
+                uint64_t *out) {
+  const uint8_t *p = enc;
+  uint64_t len = X;
+  for (size_t i = xc.b2b.size(); i-- > 0;) {
+    if (len < 4) return ZGPU_CRC_INPUT_TOO_SHORT;
+    const Codec &k = xc.b2b[i];
+    const uint8_t *c = k.at_start ? p : p + len - 4, *payload = k.at_start ? p + 4 : p;
+    len -= 4;
+    const uint32_t stored = (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16 | (uint32_t)c[3] << 24;
+    if (validate && crc32c_host(payload, len) != stored) return ZGPU_INVALID_CHECKSUM;
+    p = payload;
+  }
+  if (len != n_inner * 16) return ZGPU_SHARD_TOO_SMALL;
+  for (uint64_t q = 0; q < 2 * n_inner; q++) {
+    uint64_t v = 0;
+    for (int b = 0; b < 8; b++) v |= (uint64_t)p[q * 8 + b] << (8 * (xc.a2b.big_endian ? 7 - b : b));
+    out[q] = v;
+  }
+  for (uint64_t k = 0; k < n_inner; k++) {
+    const uint64_t off = out[2 * k], nb = out[2 * k + 1];
+    if (off == ~0ull && nb == ~0ull) continue;
+    if (off > shard_len || nb > shard_len - off) return ZGPU_SHARD_INDEX_OOB;
+  }
+  return ZGPU_OK;
+}
+
+struct Leaf {
+  uint64_t entry, j;         // its chunk's entry, its index in the chunk's leaf grid
+  uint64_t origin[ZG_MAXD];  // in the array
+  bool partial;              // partly covered: staged (else covered: read straight from the data)
+  uint64_t stage = 0;        // partial: its staging box
+  const uint8_t *old = nullptr;  // partial: the old leaf's encoded bytes on the device (null: missing)
+  uint64_t old_len = 0;
+  uint32_t nonfill = 0;
+  bool encode = false;
+  uint64_t slot = 0, enc_len = 0;  // encode: its slot and encoded length
+};
+
+int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const uint64_t *chunk_shape,
+                 const void *const *chunk_ptrs, const uint64_t *chunk_lens, const uint64_t *sel_start,
+                 const uint64_t *sel_shape, const void *data, uint32_t flags, const zgpu_store_entry **entries_out,
+                 uint64_t *n_out, zgpu_result **result_out, void *stream) {
+  zgpu_ctx *C = ch->ctx;
+  const Chain &top = *ch->chain;
+  const bool sharded = top.a2b.kind == CodecKind::Sharding;
+  if (const int rc = store_chain_check(top, nd, chunk_shape)) return rc;
+  if (zgpu_chain_encoded_bound(ch, nd, chunk_shape) < 0)
+    return set_err(ZGPU_UNSUPPORTED, "store: the chain's encoded size is not bounded");
+  const uint64_t *leaf_shape = sharded ? top.a2b.inner_shape.data() : chunk_shape;
+  StoreLayout L;
+  {
+    std::string err;
+    if (const int rc = store_classify(nd, array_shape, chunk_shape, leaf_shape, sel_start, sel_shape, L, err))
+      return set_err(rc, err);
+  }
+  if (L.chunks.empty()) return ZGPU_OK;
+  const bool enc_dev = flags & ZGPU_ENC_DEVICE, data_dev = flags & ZGPU_OUT_DEVICE;
+  const bool validate = ch->validate && !(flags & ZGPU_NO_VALIDATE);
+  const bool store_empty = flags & ZGPU_STORE_EMPTY_CHUNKS;
+  const uint32_t es = top.es;
+  if (data_dev && (uintptr_t)data % std::min<uint32_t>(es, 8))
+    return set_err(ZGPU_INVALID_ARGUMENT, "store: data is not aligned to its element size");
+  const uint64_t nE = L.chunks.size(), lpc = L.leaves_per_chunk, leaf_n = volume(leaf_shape, nd);
+  const uint64_t leaf_bytes = leaf_n * es;
+  std::shared_ptr<Chain> leaf_chain = sharded ? top.a2b.inner : ch->chain;
+  zgpu_chain leafch{C, leaf_chain, ch->validate};
+  const int64_t leaf_bound = zgpu_chain_encoded_bound(&leafch, nd, leaf_shape);
+  if (leaf_bound < 0) return set_err(ZGPU_UNSUPPORTED, "store: the chain's encoded size is not bounded");
+  const uint64_t pitch = std::max<uint64_t>(256, align_up((uint64_t)leaf_bound, 256));
+  const uint64_t X = sharded ? (uint64_t)chain_fixed_encoded_size(*top.a2b.index, lpc * 2) : 0;
+
+  HIPCHK(hipSetDevice(C->device));
+  uint64_t *ctr = call_counters();
+  std::fill(ctr, ctr + CTR_N, 0);
+  size_detail() = SizeDetail{};
+  std::unique_ptr<zgpu_result> R(new zgpu_result());
+  ctx_ref(C);
+  R->ctx = C;
+  std::vector<zgpu_store_entry> &E = R->store_entries;
+  E.assign(nE, zgpu_store_entry{});
+  for (uint64_t k = 0; k < nE; k++) E[k].chunk = L.chunks[k].lin;
+
+  // host tables the queued copies read: declared before the scratch, whose destructor waits for them
+  std::vector<uint64_t> index(sharded ? nE * lpc * 2 : 0, ~0ull), rows, starts, hsh;
+  std::vector<Leaf> leaves;
+  std::vector<zgpu_chunk_desc> descs;
+  std::vector<ZgOverlayBox> boxes;
+  std::vector<ZgItem> items;
+  std::vector<uint32_t> nf;
+  LaneScope ls(C);
+  hipStream_t s = pick_stream(ls.L, stream);
+  Scratch sc(C, s);
+
+  // the data and the old chunks the subset does not cover, on the device
+  const uint64_t data_bytes = volume(sel_shape, nd) * es;
+  const uint8_t *d_data = (const uint8_t *)data;
+  if (!data_dev) {
+    uint8_t *d = sc.dev<uint8_t>(data_bytes);
+    HIPCHK(hipMemcpyAsync(d, data, data_bytes, hipMemcpyHostToDevice, s));
+    d_data = d;
+  }
+  std::vector<const uint8_t *> old(nE, nullptr);
+  std::vector<uint64_t> old_len(nE, 0);
+  {
+    constexpr uint64_t HR = 64;  // readable bytes either side of an old chunk (launch_unpackbits)
+    uint64_t total = 0;
+    std::vector<uint64_t> off(nE, 0);
+    for (uint64_t k = 0; k < nE; k++) {
+      const uint64_t lin = L.chunks[k].lin;
+      if (L.chunks[k].covered || !chunk_ptrs[lin]) continue;
+      old_len[k] = chunk_lens[lin];
+      off[k] = total + HR;
+      total += align_up(HR + old_len[k] + HR, 256);
+    }
+    uint8_t *pack = (!enc_dev && total) ? sc.dev<uint8_t>(total) : nullptr;
+    for (uint64_t k = 0; k < nE; k++) {
+      const uint64_t lin = L.chunks[k].lin;
+      if (L.chunks[k].covered || !chunk_ptrs[lin]) continue;
+      if (enc_dev) {
+        old[k] = (const uint8_t *)chunk_ptrs[lin];
+      } else {
+        old[k] = pack + off[k];
+        if (old_len[k]) HIPCHK(hipMemcpyAsync(pack + off[k], chunk_ptrs[lin], old_len[k], hipMemcpyHostToDevice, s));
+      }
+    }
+  }
+
+  // the old shards' indexes, decoded and range-checked on the host
+  if (sharded) {
+    const Chain &xc = *top.a2b.index;
+    uint8_t *hx = nullptr;
+    if (enc_dev) {
+      hx = sc.pinned<uint8_t>(std::max<uint64_t>(nE * X, 1));
+      for (uint64_t k = 0; k < nE; k++)
+        if (old[k] && old_len[k] >= X)
+          HIPCHK(hipMemcpyAsync(hx + k * X, old[k] + (top.a2b.at_start ? 0 : old_len[k] - X), X, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+    }
+    for (uint64_t k = 0; k < nE; k++) {
+      if (!old[k]) continue;
+      if (old_len[k] < X) {
+        E[k].status = ZGPU_SHARD_TOO_SMALL;
+        continue;
+      }
+      const uint8_t *src = enc_dev ? hx + k * X
+                                   : (const uint8_t *)chunk_ptrs[L.chunks[k].lin] + (top.a2b.at_start ? 0 : old_len[k] - X);
+      E[k].status = parse_index(src, X, xc, lpc, validate, old_len[k], index.data() + k * lpc * 2);
+    }
+  }
+
+  // the leaves the subset touches
+  uint64_t n_stage = 0;
+  for (uint64_t k = 0; k < nE; k++) {
+    if (E[k].status) continue;
+    for (uint64_t j = 0; j < lpc; j++) {
+      const uint8_t cls = L.leaf_class[L.chunks[k].first_leaf + j];
+      if (cls == ZGPU_LEAF_UNTOUCHED) continue;
+      Leaf lf{};
+      lf.entry = k;
+      lf.j = j;
+      store_leaf_origin(L, L.chunks[k], leaf_shape, j, lf.origin);
+      lf.partial = cls == ZGPU_LEAF_PARTIAL;
+      if (lf.partial) {
+        lf.stage = n_stage++;
+        if (!sharded) {
+          lf.old = old[k];
+          lf.old_len = old_len[k];
+        } else if (old[k] && index[(k * lpc + j) * 2] != ~0ull) {
+          lf.old = old[k] + index[(k * lpc + j) * 2];
+          lf.old_len = index[(k * lpc + j) * 2 + 1];
+        }
+      }
+      leaves.push_back(lf);
+    }
+  }
+
+  // one decode batch of the partly covered leaves into the staging array, one overlay launch
+  uint64_t stage_shape[ZG_MAXD], stage_stride[ZG_MAXD], sel_stride[ZG_MAXD];
+  for (uint32_t d = 0; d < nd; d++) stage_shape[d] = leaf_shape[d];
+  stage_shape[0] = std::max<uint64_t>(n_stage, 1) * leaf_shape[0];
+  for (int d = (int)nd - 1; d >= 0; d--) {
+    stage_stride[d] = d == (int)nd - 1 ? 1 : stage_stride[d + 1] * stage_shape[d + 1];
+    sel_stride[d] = d == (int)nd - 1 ? 1 : sel_stride[d + 1] * sel_shape[d + 1];
+  }
+  uint8_t *staging = n_stage ? sc.dev<uint8_t>(n_stage * leaf_bytes) : nullptr;
+  if (n_stage) {
+    std::vector<uint64_t> owner;
+    for (const Leaf &lf : leaves) {
+      if (!lf.partial) continue;
+      zgpu_chunk_desc D{};
+      D.enc = lf.old;
+      D.enc_len = lf.old ? lf.old_len : 0;
+      for (uint32_t d = 0; d < nd; d++) {
+        D.chunk_shape[d] = D.sel_shape[d] = leaf_shape[d];
+        D.out_start[d] = d == 0 ? lf.stage * leaf_shape[0] : 0;
+      }
+      descs.push_back(D);
+      owner.push_back(lf.entry);
+      if (lf.old) ctr[CTR_STORE_DECODED]++;
+    }
+    GeneralCall G{C, validate, nd, staging, stage_shape, (flags & ZGPU_NO_VALIDATE) | ZGPU_ENC_DEVICE | ZGPU_OUT_DEVICE,
+                  s, {}};
+    std::vector<int32_t> st(descs.size(), 0);
+    decode_general(G, leaf_chain, descs.data(), descs.size(), st.data());
+    HIPCHK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < st.size(); i++)
+      if (st[i] && !E[owner[i]].status) E[owner[i]].status = st[i];
+    // the overlap of every staged leaf of a chunk still in good standing
+    rows.push_back(0);
+    for (const Leaf &lf : leaves) {
+      if (!lf.partial || E[lf.entry].status) continue;
+      ZgOverlayBox B{};
+      uint64_t so = 0, dof = lf.stage * leaf_shape[0] * stage_stride[0], nr = 1;
+      for (uint32_t d = 0; d < nd; d++) {
+        const uint64_t lo = std::max(lf.origin[d], sel_start[d]);
+        const uint64_t hi = std::min(lf.origin[d] + leaf_shape[d], sel_start[d] + sel_shape[d]);
+        B.ext[d] = hi - lo;
+        B.src_stride[d] = sel_stride[d];
+        B.dst_stride[d] = stage_stride[d];
+        so += (lo - sel_start[d]) * sel_stride[d];
+        dof += (lo - lf.origin[d]) * stage_stride[d];
+        if (d + 1 < nd) nr *= B.ext[d];
+      }
+      B.src = (uint64_t)(d_data + so * es);
+      B.dst = (uint64_t)(staging + dof * es);
+      boxes.push_back(B);
+      rows.push_back(rows.back() + nr);
+    }
+    if (!boxes.empty()) {
+      ZgOverlayBox *d_boxes = sc.dev<ZgOverlayBox>(boxes.size());
+      uint64_t *d_rows = sc.dev<uint64_t>(rows.size());
+      HIPCHK(hipMemcpyAsync(d_boxes, boxes.data(), boxes.size() * sizeof(ZgOverlayBox), hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, s));
+      HIPCHK(launch_subset_overlay(d_boxes, d_rows, (uint32_t)boxes.size(), rows.back(), nd, es, s));
+    }
+  }
+
+  // the leaves to go on with, staged ones first; their origins in the array each group reads
+  std::vector<Leaf *> group[2];  // [0] staged (array: the staging array), [1] covered (array: the data)
+  for (Leaf &lf : leaves)
+    if (!E[lf.entry].status) group[lf.partial ? 0 : 1].push_back(&lf);
+  const void *g_array[2] = {staging, d_data};
+  const uint64_t *g_shape[2] = {stage_shape, sel_shape};
+  auto leaf_start = [&](const Leaf &lf, uint32_t d) {
+    return lf.partial ? (d == 0 ? lf.stage * leaf_shape[0] : 0) : lf.origin[d] - sel_start[d];
+  };
+
+  // rule 3: which leaves equal the fill value everywhere (bytewise, k_fill_check)
+  {
+    const uint64_t n_all = group[0].size() + group[1].size();
+    starts.resize(std::max<uint64_t>(n_all * nd, 1));
+    uint64_t q = 0;
+    for (int g = 0; g < 2; g++)
+      for (const Leaf *lf : group[g])
+        for (uint32_t d = 0; d < nd; d++) starts[q++] = leaf_start(*lf, d);
+    uint64_t *d_starts = sc.dev<uint64_t>(starts.size());
+    uint32_t *d_nf = sc.dev<uint32_t>(std::max<uint64_t>(n_all, 1));
+    uint32_t *h_nf = sc.pinned<uint32_t>(std::max<uint64_t>(n_all, 1));
+    HIPCHK(hipMemcpyAsync(d_starts, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, s));
+    uint64_t base = 0;
+    for (int g = 0; g < 2; g++) {
+      ZgEncode P{};
+      P.nd = nd;
+      P.es = es;
+      P.nelem = leaf_n;
+      std::memcpy(P.fill, top.fill, sizeof(P.fill));
+      for (uint32_t d = 0; d < nd; d++) {
+        P.dec_shape[d] = leaf_shape[d];
+        P.array_shape[d] = g_shape[g][d];
+        P.array_stride[d] = g == 0 ? stage_stride[d] : sel_stride[d];
+      }
+      if (!group[g].empty())
+        HIPCHK(launch_fill_check(d_starts + base * nd, (const uint8_t *)g_array[g], P, (uint32_t)group[g].size(),
+                                 d_nf + base, s));
+      base += group[g].size();
+    }
+    if (n_all) HIPCHK(hipMemcpyAsync(h_nf, d_nf, n_all * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    q = 0;
+    for (int g = 0; g < 2; g++)
+      for (Leaf *lf : group[g]) {
+        lf->nonfill = h_nf[q++];
+        lf->encode = lf->nonfill || (!sharded && store_empty);
+      }
+  }
+
+  // encode: unsharded chunks straight into the output, inner chunks into slots for the shard layout
+  uint64_t n_enc = 0;
+  for (Leaf &lf : leaves)
+    if (lf.encode) lf.slot = n_enc++;
+  uint8_t *out_dev = nullptr;  // the encoded chunks on the device
+  uint8_t *slots = nullptr;
+  if (!sharded) {
+    if (enc_dev && n_enc) out_dev = R->dev = (uint8_t *)C->dev_alloc(n_enc * pitch);
+    else if (n_enc) out_dev = sc.dev<uint8_t>(n_enc * pitch);
+    slots = out_dev;
+  } else if (n_enc) {
+    slots = sc.dev<uint8_t>(n_enc * pitch);
+  }
+  for (int g = 0; g < 2; g++) {
+    std::vector<zgpu_encode_desc> ed;
+    std::vector<Leaf *> who;
+    for (Leaf *lf : group[g]) {
+      if (!lf->encode) continue;
+      zgpu_encode_desc D{};
+      D.dst = slots + lf->slot * pitch;
+      D.dst_cap = (uint64_t)leaf_bound;
+      for (uint32_t d = 0; d < nd; d++) D.chunk_start[d] = leaf_start(*lf, d);
+      ed.push_back(D);
+      who.push_back(lf);
+    }
+    if (ed.empty()) continue;
+    std::vector<uint64_t> lens(ed.size(), 0);
+    if (const int rc = encode_chunks_on(&leafch, nd, leaf_shape, g_array[g], g_shape[g], ed.data(), ed.size(),
+                                        lens.data(), s))
+      return rc;
+    for (size_t i = 0; i < who.size(); i++) who[i]->enc_len = lens[i];
+    ctr[CTR_STORE_ENCODED] += ed.size();
+  }
+
+  // what every entry becomes; a shard is laid out from one item per inner chunk
+  std::vector<uint64_t> e_off(nE, 0);  // the entry's bytes in out_dev
+  if (!sharded) {
+    for (const Leaf &lf : leaves) {
+      if (E[lf.entry].status) continue;
+      E[lf.entry].action = lf.encode ? ZGPU_STORE_SET : ZGPU_STORE_ERASE;
+      E[lf.entry].enc_len = lf.encode ? lf.enc_len : 0;
+      e_off[lf.entry] = lf.slot * pitch;
+    }
+  } else {
+    const Chain &xc = *top.a2b.index;
+    std::vector<const Leaf *> of(nE * lpc, nullptr);
+    for (const Leaf &lf : leaves) of[lf.entry * lpc + lf.j] = &lf;
+    std::vector<uint64_t> set;  // the entries that get a new shard
+    uint64_t total = 0, cap = 0;
+    for (uint64_t k = 0; k < nE; k++) {
+      if (E[k].status) continue;
+      uint64_t present = 0, bytes = X;
+      const size_t first = items.size();
+      for (uint64_t j = 0; j < lpc; j++) {
+        ZgItem it{};
+        uint32_t f = 0;
+        if (const Leaf *lf = of[k * lpc + j]) {  // touched: newly encoded, or all fill and omitted
+          if (lf->encode) {
+            it.src = (uint64_t)(slots + lf->slot * pitch);
+            it.len = lf->enc_len;
+            f = 1;
+          }
+        } else if (old[k] && index[(k * lpc + j) * 2] != ~0ull) {  // untouched and present: carried over
+          it.src = (uint64_t)(old[k] + index[(k * lpc + j) * 2]);
+          it.len = index[(k * lpc + j) * 2 + 1];
+          f = 1;
+          ctr[CTR_STORE_CARRIED]++;
+        }
+        items.push_back(it);
+        nf.push_back(f);
+        present += f;
+        bytes += f ? it.len : 0;
+      }
+      if (!present) {  // no inner chunk left: the shard is erased
+        E[k].action = ZGPU_STORE_ERASE;
+        items.resize(first);
+        nf.resize(first);
+        continue;
+      }
+      E[k].action = ZGPU_STORE_SET;
+      E[k].enc_len = bytes;
+      e_off[k] = total;
+      total += align_up(bytes, 256);
+      cap = std::max(cap, bytes);
+      set.push_back(k);
+    }
+    const uint64_t nS = set.size();
+    if (nS) {
+      out_dev = enc_dev ? (R->dev = (uint8_t *)C->dev_alloc(total)) : sc.dev<uint8_t>(total);
+      hsh.resize(nS);
+      for (uint64_t i = 0; i < nS; i++) hsh[i] = (uint64_t)(out_dev + e_off[set[i]]);
+      ZgItem *d_items = sc.dev<ZgItem>(items.size());
+      uint32_t *d_nf = sc.dev<uint32_t>(nf.size() + items.size() + nS);
+      uint32_t *d_ist = d_nf + nf.size(), *d_shst = d_ist + items.size();
+      uint64_t *d_sh = sc.dev<uint64_t>(3 * nS + items.size());
+      uint64_t *d_index_ptr = d_sh + nS, *d_len = d_sh + 2 * nS, *d_off = d_sh + 3 * nS;
+      HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(ZgItem), hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(d_nf, nf.data(), nf.size() * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemsetAsync(d_ist, 0, (items.size() + nS) * 4, s));
+      HIPCHK(hipMemcpyAsync(d_sh, hsh.data(), nS * 8, hipMemcpyHostToDevice, s));
+      int n_pre = 0;
+      for (const Codec &k : xc.b2b) n_pre += k.at_start ? 1 : 0;
+      ZgShardLayoutArgs A{lpc, 0, cap, X, 4ull * n_pre, top.a2b.at_start ? 1u : 0u, xc.a2b.big_endian ? 1u : 0u};
+      HIPCHK(launch_shard_layout_var((uint32_t)items.size(), d_nf, d_items, d_ist, A, d_sh, d_off, d_index_ptr, d_len,
+                                     d_shst, (uint32_t)nS, s));
+      uint64_t lo = 4ull * n_pre, len = lpc * 16;
+      for (const Codec &k : xc.b2b) {
+        HIPCHK(launch_crc32c_encode(d_index_ptr, (uint32_t)nS, lo, len, k.at_start ? 1 : 0, s));
+        if (k.at_start) lo -= 4;
+        len += 4;
+      }
+      uint64_t *h_len = sc.pinned<uint64_t>(2 * nS);
+      HIPCHK(hipMemcpyAsync(h_len, d_len, nS * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(h_len + nS, d_shst, nS * 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      for (uint64_t i = 0; i < nS; i++)
+        if (((const uint32_t *)(h_len + nS))[i] || h_len[i] != E[set[i]].enc_len)
+          return set_err(ZGPU_HIP_ERROR, "store: the shard layout disagrees with the host's");
+    }
+  }
+
+  // the encoded chunks to where the caller reads them
+  if (enc_dev) {
+    for (uint64_t k = 0; k < nE; k++)
+      if (E[k].action == ZGPU_STORE_SET) E[k].enc = out_dev + e_off[k];
+  } else {
+    uint64_t total = 0;
+    std::vector<uint64_t> h_off(nE, 0);
+    for (uint64_t k = 0; k < nE; k++)
+      if (E[k].action == ZGPU_STORE_SET) {
+        h_off[k] = total;
+        total += align_up(std::max<uint64_t>(E[k].enc_len, 1), 64);
+      }
+    R->own = (uint8_t *)C->host_alloc(std::max<uint64_t>(total, 1));
+    for (uint64_t k = 0; k < nE; k++)
+      if (E[k].action == ZGPU_STORE_SET) {
+        if (E[k].enc_len)
+          HIPCHK(hipMemcpyAsync(R->own + h_off[k], out_dev + e_off[k], E[k].enc_len, hipMemcpyDeviceToHost, s));
+        E[k].enc = R->own + h_off[k];
+      }
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  int rc = 0;
+  for (uint64_t k = 0; k < nE && !rc; k++) rc = E[k].status;
+  *entries_out = E.data();
+  *n_out = nE;
+  *result_out = R.release();
+  if (rc) set_err(rc, std::string("store: ") + zgpu_status_name(rc));
+  return rc;
+}
+
+}  // namespace
+
+extern "C" int zgpu_store_entry_copy(zgpu_chain *ch, const zgpu_store_entry *e, void *dst, void *stream) {
+  ABI_GUARD_BEGIN
+  if (!ch || !e || (e->enc_len && (!e->enc || !dst))) return set_err(ZGPU_INVALID_ARGUMENT, "NULL argument");
+  if (!e->enc_len) return ZGPU_OK;
+  HIPCHK(hipSetDevice(ch->ctx->device));
+  LaneScope ls(ch->ctx);
+  hipStream_t s = pick_stream(ls.L, stream);
+  HIPCHK(hipMemcpyAsync(dst, e->enc, e->enc_len, hipMemcpyDefault, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return ZGPU_OK;
+  ABI_GUARD_END
+}
+
+extern "C" int zgpu_store_array_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape,
+                                       const uint64_t *chunk_shape, const void *const *chunk_ptrs,
+                                       const uint64_t *chunk_lens, const uint64_t *sel_start, const uint64_t *sel_shape,
+                                       const void *data, uint32_t flags, const zgpu_store_entry **entries,
+                                       uint64_t *n_entries, zgpu_result **result, void *stream) {
+  ABI_GUARD_BEGIN
+  if (entries) *entries = nullptr;
+  if (n_entries) *n_entries = 0;
+  if (result) *result = nullptr;
+  if (!ch || !array_shape || !chunk_shape || !chunk_ptrs || !chunk_lens || !sel_start || !sel_shape || !entries ||
+      !n_entries || !result)
+    return set_err(ZGPU_INVALID_ARGUMENT, "NULL argument");
+  if (nd == 0 || nd > ZGPU_MAX_DIMS) return set_err(ZGPU_INVALID_ARGUMENT, "ndim out of range");
+  if (!data && volume(sel_shape, nd)) return set_err(ZGPU_INVALID_ARGUMENT, "NULL argument");
+  return store_subset(ch, nd, array_shape, chunk_shape, chunk_ptrs, chunk_lens, sel_start, sel_shape, data, flags,
+                      entries, n_entries, result, stream);
+  ABI_GUARD_END
+}

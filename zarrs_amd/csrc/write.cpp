@@ -530,9 +530,9 @@ static int check_origins(uint32_t nd, const uint64_t *array_shape, const zgpu_en
 
 // zgpu_encode_chunks (arguments checked) on stream s of the caller's lane: n chunks of the device array to their device
 // destinations, synchronous (the temporaries go back when it returns).
-static int encode_chunks_on(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, const void *array,
-                            const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n,
-                            uint64_t *enc_lens, hipStream_t s) {
+int encode_chunks_on(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, const void *array,
+                     const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint64_t *enc_lens,
+                     hipStream_t s) {
   if (!n) return ZGPU_OK;
   zgpu_ctx *C = ch->ctx;
   Scratch sc(C, s);
