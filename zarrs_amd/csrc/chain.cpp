@@ -463,16 +463,6 @@ std::shared_ptr<Chain> parse_chain(const Json &codecs, const std::string &dt, co
   return parse(codecs, dt, es, comp, fill);
 }
 
-int64_t chain_fixed_encoded_size(const Chain &c, uint64_t nelem) {
-  if (c.a2b.kind != CodecKind::Bytes && c.a2b.kind != CodecKind::PackBits) return -1;
-  int64_t n = (int64_t)(c.a2b.kind == CodecKind::PackBits ? packbits_size(c.a2b, nelem) : nelem * c.enc_es);
-  for (const Codec &k : c.b2b) {
-    if (is_checksum(k.kind)) n += 4;
-    else if (k.kind != CodecKind::Shuffle) return -1;
-  }
-  return n;
-}
-
 uint64_t gzip_bound(uint64_t n) { return n + 10 + 8 + (n + 7) / 8 + (n + 63) / 64 + 5; }
 
 // ZlibCodec::encoded_representation (zlib/zlib_codec.rs): zlib's compressBound
@@ -485,19 +475,33 @@ uint64_t zstd_bound(uint64_t n) { return n + 4 + 14 + 4 + 3 * ((n + 999) / 1000)
 // Bz2Codec::encoded_representation (bz2/bz2_codec.rs)
 uint64_t bz2_bound(uint64_t n) { return n + n / 8 + 1024; }
 
-int64_t chain_encoded_bound(const Chain &c, uint64_t nelem) {
-  if (c.a2b.kind != CodecKind::Bytes && c.a2b.kind != CodecKind::PackBits) return -1;
-  uint64_t n = c.a2b.kind == CodecKind::PackBits ? packbits_size(c.a2b, nelem) : nelem * c.enc_es;
-  for (const Codec &k : c.b2b) {
-    if (is_checksum(k.kind)) n += 4;
-    else if (k.kind == CodecKind::Gzip) n = gzip_bound(n);
-    else if (k.kind == CodecKind::Zlib) n = zlib_bound(n);
-    else if (k.kind == CodecKind::Zstd) n = zstd_bound(n);
-    else if (k.kind == CodecKind::Bz2) n = bz2_bound(n);
-    else if (k.kind == CodecKind::Blosc) n += 16;  // BLOSC_MAX_OVERHEAD (blosc_via_blosc_src.rs:80)
-    else if (k.kind != CodecKind::Shuffle) return -1;
+int64_t codec_encoded_bound(const Codec &k, uint64_t n, bool *fixed) {
+  if (is_checksum(k.kind)) return (int64_t)(n + 4);
+  if (k.kind == CodecKind::Shuffle) return (int64_t)n;
+  if (fixed) *fixed = false;
+  switch (k.kind) {
+    case CodecKind::Gzip: return (int64_t)gzip_bound(n);
+    case CodecKind::Zlib: return (int64_t)zlib_bound(n);  // k_gzip_encode keeps to it (zlib_bounded)
+    case CodecKind::Zstd: return (int64_t)zstd_bound(n);
+    case CodecKind::Bz2: return (int64_t)bz2_bound(n);
+    case CodecKind::Blosc: return (int64_t)(n + 16);  // BLOSC_MAX_OVERHEAD (blosc_via_blosc_src.rs:80)
+    default: return -1;
   }
-  return (int64_t)n;
 }
+
+// the array->bytes codec's bytes through every bytes->bytes codec; -1 if unbounded, or not fixed when asked
+static int64_t chain_size(const Chain &c, uint64_t nelem, bool want_fixed) {
+  if (c.a2b.kind != CodecKind::Bytes && c.a2b.kind != CodecKind::PackBits) return -1;
+  int64_t n = (int64_t)(c.a2b.kind == CodecKind::PackBits ? packbits_size(c.a2b, nelem) : nelem * c.enc_es);
+  bool fixed = true;
+  for (const Codec &k : c.b2b) {
+    n = codec_encoded_bound(k, (uint64_t)n, &fixed);
+    if (n < 0 || (want_fixed && !fixed)) return -1;
+  }
+  return n;
+}
+
+int64_t chain_fixed_encoded_size(const Chain &c, uint64_t nelem) { return chain_size(c, nelem, true); }
+int64_t chain_encoded_bound(const Chain &c, uint64_t nelem) { return chain_size(c, nelem, false); }
 
 }  // namespace zgpu

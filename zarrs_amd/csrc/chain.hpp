@@ -101,6 +101,10 @@ int64_t chain_fixed_encoded_size(const Chain &c, uint64_t nelem);
 // ZstdCodec's (zstd_codec.rs:132-147), bz2 as Bz2Codec's (bz2_codec.rs: size + size / 8 + 1024); -1 if
 // unbounded.
 int64_t chain_encoded_bound(const Chain &c, uint64_t nelem);
+// One bytes->bytes codec's encoded size for n bytes in, the one statement of the per-stage arithmetic the
+// two functions above and the write path's layout (encode_layout.cpp) read: exact for the checksums and
+// numcodecs.shuffle, else a bound (*fixed, if given, is cleared); -1 for a codec without one.
+int64_t codec_encoded_bound(const Codec &k, uint64_t n, bool *fixed = nullptr);
 uint64_t gzip_bound(uint64_t n);
 uint64_t zlib_bound(uint64_t n);
 uint64_t zstd_bound(uint64_t n);

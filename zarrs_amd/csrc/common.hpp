@@ -104,6 +104,11 @@ struct ZgIndexSpec {
   uint32_t verify;       // validate_checksums
 };
 
+// blosc (c-blosc 1.x frames): a frame's compressor, as the decoder reads it from the header and the
+// write path's layout (encode_layout.hpp) names it to the encoder
+enum : uint32_t { BL_COMP_BLOSCLZ = 0, BL_COMP_LZ4 = 1, BL_COMP_SNAPPY = 2, BL_COMP_ZLIB = 3, BL_COMP_ZSTD = 4, BL_COMP_MEMCPY = 0x100,
+                  BL_COMP_SKIP = 0xFFFFFFFFu };
+
 }  // namespace zgpu
 
 // device status codes (== zgpu.h)

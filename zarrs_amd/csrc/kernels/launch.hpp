@@ -305,8 +305,7 @@ hipError_t launch_packbits(const uint64_t *tab, uint32_t n_chunks, const ZgPackB
 
 // blosc (c-blosc 1.x frames): stream table built on the device, sized on the host from BlInfo (first
 // execution of a plan) or from the capacities that execution recorded (later executions)
-enum : uint32_t { BL_COMP_BLOSCLZ = 0, BL_COMP_LZ4 = 1, BL_COMP_SNAPPY = 2, BL_COMP_ZLIB = 3, BL_COMP_ZSTD = 4, BL_COMP_MEMCPY = 0x100,
-                  BL_COMP_SKIP = 0xFFFFFFFFu };
+// (BL_COMP_*, a frame's compressor: common.hpp)
 #define BL_SKIP 0x100u  // stream status: not (yet) decoded by the zstd pipeline / a stream decoder
 enum : uint32_t { BL_KIND_RAW = 0, BL_KIND_LZ4 = 1, BL_KIND_SNAPPY = 2, BL_KIND_ZLIB = 3, BL_KIND_ZSTD = 4,
                   BL_KIND_BLOSCLZ = 5 };

@@ -12,6 +12,7 @@
 #include "chain.hpp"
 #include "common.hpp"
 #include "ctx.hpp"
+#include "encode_layout.hpp"
 #include "kernels/launch.hpp"
 #include "plan_layout.hpp"
 
@@ -222,8 +223,22 @@ std::shared_ptr<Chain> strip_value_codecs(const Chain &c, std::vector<Codec> &st
 void retype_stripped(Chain &c, const Chain &original);
 uint8_t *value_encode_elements(const std::vector<Codec> &steps, const uint8_t *in, uint64_t n, Scratch &sc,
                                hipStream_t s);
-// write.cpp: zgpu_encode_chunks (arguments checked) on stream s, synchronous
+// write.cpp: zgpu_encode_chunks (arguments checked) on stream s, synchronous; fixed_only: refuse a chain
+// whose chunks vary in length (zgpu_encode_batch)
 int encode_chunks_on(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, const void *array,
                      const uint64_t *array_shape, const zgpu_encode_desc *descs, uint64_t n, uint64_t *enc_lens,
-                     hipStream_t s);
+                     hipStream_t s, bool fixed_only = false);
+// The checksum codecs of an ENC_FIXED layout in place over n device buffers (d_dst on the device): each
+// covers [lo, lo + in_bound) of every buffer and writes its value in front of or behind them.
+void checksums_in_place(const uint64_t *d_dst, uint32_t n, const EncodeLayout &L, hipStream_t s);
+// The device tables that lay out n shards of n_chunks inner chunks in all and the launch's arguments from
+// the sharded layout L: dst = h_dst (copied on s); the launch fills off, index_ptr and len; nf: nf_words
+// words, the fill flags first. Then checksums_in_place(index_ptr, n, *L.index, s) finishes the shards.
+struct ShardTables {
+  uint64_t *dst, *index_ptr, *len, *off;
+  uint32_t *nf;
+  ZgShardLayoutArgs A;
+};
+ShardTables shard_tables(Scratch &sc, const EncodeLayout &L, const uint64_t *h_dst, uint64_t n, uint64_t n_chunks,
+                         uint64_t nf_words, uint64_t E, uint64_t E_pitch, hipStream_t s);
 #pragma GCC visibility pop

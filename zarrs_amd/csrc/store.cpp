@@ -56,52 +56,6 @@ uint32_t crc32c_host(const uint8_t *p, size_t n) {
 
 uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
-// What encode_fixed / encode_var / encode_packbits (write.cpp) take, checked without the device.
-int leaf_chain_check(const Chain &c, uint32_t nd, bool packbits_ok) {
-  if (c.a2b.kind == CodecKind::PackBits ? !packbits_ok : c.a2b.kind != CodecKind::Bytes)
-    return set_err(ZGPU_UNSUPPORTED, "store: array->bytes codec must be bytes (or packbits, unsharded)");
-  for (const Codec &k : c.a2a)
-    if (k.kind == CodecKind::Transpose && k.order.size() != nd)
-      return set_err(ZGPU_INVALID_ARGUMENT, "transpose order rank != ndim");
-  const uint32_t es = c.a2b.kind == CodecKind::PackBits ? 1 : c.enc_es;
-  bool var_len = false;
-  for (size_t i = 0; i < c.b2b.size(); i++) {
-    const Codec &k = c.b2b[i];
-    if (k.kind == CodecKind::Shuffle && i == 0 && k.elementsize == es) continue;
-    if (is_checksum(k.kind)) continue;
-    if (k.kind == CodecKind::Gzip || k.kind == CodecKind::Zlib || k.kind == CodecKind::Zstd) {
-      var_len = true;
-      continue;
-    }
-    if (k.kind == CodecKind::Blosc && !var_len &&
-        (k.cname == "lz4" || k.cname == "lz4hc" || k.cname == "zstd" || k.cname == "blosclz" || k.cname == "zlib" ||
-         k.cname == "snappy")) {
-      var_len = true;
-      continue;
-    }
-    if (k.kind == CodecKind::Bz2) return set_err(ZGPU_UNSUPPORTED, "store: numcodecs.bz2 is decode-only on the GPU");
-    return set_err(ZGPU_UNSUPPORTED, "store: the chain has a codec the GPU write path does not encode");
-  }
-  return ZGPU_OK;
-}
-
-int store_chain_check(const Chain &top, uint32_t nd, const uint64_t *chunk_shape) {
-  if (top.a2b.kind != CodecKind::Sharding) return leaf_chain_check(top, nd, true);
-  if (!top.a2a.empty() || !top.b2b.empty()) return set_err(ZGPU_UNSUPPORTED, "store: codecs around sharding_indexed");
-  const Chain &inner = *top.a2b.inner, &xc = *top.a2b.index;
-  if (inner.a2b.kind == CodecKind::Sharding) return set_err(ZGPU_UNSUPPORTED, "store: nested sharding_indexed");
-  if (chain_has_value_codec(inner)) return set_err(ZGPU_UNSUPPORTED, "store: value codecs inside sharding_indexed");
-  if (xc.a2b.kind != CodecKind::Bytes || !xc.a2a.empty())
-    return set_err(ZGPU_UNSUPPORTED, "index_codecs must be bytes (+crc32c)");
-  for (const Codec &k : xc.b2b)
-    if (k.kind != CodecKind::Crc32c) return set_err(ZGPU_UNSUPPORTED, "index_codecs must be bytes (+crc32c)");
-  if (top.a2b.inner_shape.size() != nd) return set_err(ZGPU_INVALID_ARGUMENT, "sharding chunk_shape rank");
-  for (uint32_t d = 0; d < nd; d++)
-    if (!top.a2b.inner_shape[d] || chunk_shape[d] % top.a2b.inner_shape[d])
-      return set_err(ZGPU_INVALID_ARGUMENT, "shard shape not a multiple of chunk_shape");
-  return leaf_chain_check(inner, nd, false);
-}
-
 // An encoded shard index (X bytes: bytes{endian} + crc32c codecs) decoded on the host into n_inner
 // (offset, nbytes) pairs, every present entry checked against the shard's length.
 int parse_index(const uint8_t *enc, uint64_t X, const Chain &xc, uint64_t n_inner, bool validate, uint64_t shard_len,
@@ -150,9 +104,14 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
   zgpu_ctx *C = ch->ctx;
   const Chain &top = *ch->chain;
   const bool sharded = top.a2b.kind == CodecKind::Sharding;
-  if (const int rc = store_chain_check(top, nd, chunk_shape)) return rc;
-  if (zgpu_chain_encoded_bound(ch, nd, chunk_shape) < 0)
-    return set_err(ZGPU_UNSUPPORTED, "store: the chain's encoded size is not bounded");
+  // what the store path does not take on top of the write path's own refusals (encode_layout throws
+  // them, ChainError, before any device work): read-modify-write goes one level deep, in one data type
+  if (sharded && top.a2b.inner->a2b.kind == CodecKind::Sharding)
+    return set_err(ZGPU_UNSUPPORTED, "store: nested sharding_indexed");
+  if (sharded && chain_has_value_codec(*top.a2b.inner))
+    return set_err(ZGPU_UNSUPPORTED, "store: value codecs inside sharding_indexed");
+  const EncodeLayout EL = encode_layout(top, nd, chunk_shape);
+  const EncodeLayout &leaf_layout = sharded ? *EL.inner : EL;
   const uint64_t *leaf_shape = sharded ? top.a2b.inner_shape.data() : chunk_shape;
   StoreLayout L;
   {
@@ -171,10 +130,9 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
   const uint64_t leaf_bytes = leaf_n * es;
   std::shared_ptr<Chain> leaf_chain = sharded ? top.a2b.inner : ch->chain;
   zgpu_chain leafch{C, leaf_chain, ch->validate};
-  const int64_t leaf_bound = zgpu_chain_encoded_bound(&leafch, nd, leaf_shape);
-  if (leaf_bound < 0) return set_err(ZGPU_UNSUPPORTED, "store: the chain's encoded size is not bounded");
-  const uint64_t pitch = std::max<uint64_t>(256, align_up((uint64_t)leaf_bound, 256));
-  const uint64_t X = sharded ? (uint64_t)chain_fixed_encoded_size(*top.a2b.index, lpc * 2) : 0;
+  const uint64_t leaf_bound = leaf_layout.size;
+  const uint64_t pitch = std::max<uint64_t>(256, align_up(leaf_bound, 256));
+  const uint64_t X = sharded ? EL.index->size : 0;
 
   HIPCHK(hipSetDevice(C->device));
   uint64_t *ctr = call_counters();
@@ -411,7 +369,7 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
       if (!lf->encode) continue;
       zgpu_encode_desc D{};
       D.dst = slots + lf->slot * pitch;
-      D.dst_cap = (uint64_t)leaf_bound;
+      D.dst_cap = leaf_bound;
       for (uint32_t d = 0; d < nd; d++) D.chunk_start[d] = leaf_start(*lf, d);
       ed.push_back(D);
       who.push_back(lf);
@@ -435,7 +393,6 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
       e_off[lf.entry] = lf.slot * pitch;
     }
   } else {
-    const Chain &xc = *top.a2b.index;
     std::vector<const Leaf *> of(nE * lpc, nullptr);
     for (const Leaf &lf : leaves) of[lf.entry * lpc + lf.j] = &lf;
     std::vector<uint64_t> set;  // the entries that get a new shard
@@ -483,27 +440,17 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
       hsh.resize(nS);
       for (uint64_t i = 0; i < nS; i++) hsh[i] = (uint64_t)(out_dev + e_off[set[i]]);
       ZgItem *d_items = sc.dev<ZgItem>(items.size());
-      uint32_t *d_nf = sc.dev<uint32_t>(nf.size() + items.size() + nS);
-      uint32_t *d_ist = d_nf + nf.size(), *d_shst = d_ist + items.size();
-      uint64_t *d_sh = sc.dev<uint64_t>(3 * nS + items.size());
-      uint64_t *d_index_ptr = d_sh + nS, *d_len = d_sh + 2 * nS, *d_off = d_sh + 3 * nS;
+      // (A.E_pitch: the largest shard; the item and shard statuses behind the fill flags)
+      const ShardTables T = shard_tables(sc, EL, hsh.data(), nS, items.size(), nf.size() + items.size() + nS, 0, cap, s);
+      uint32_t *d_ist = T.nf + nf.size(), *d_shst = d_ist + items.size();
       HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(ZgItem), hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(d_nf, nf.data(), nf.size() * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(T.nf, nf.data(), nf.size() * 4, hipMemcpyHostToDevice, s));
       HIPCHK(hipMemsetAsync(d_ist, 0, (items.size() + nS) * 4, s));
-      HIPCHK(hipMemcpyAsync(d_sh, hsh.data(), nS * 8, hipMemcpyHostToDevice, s));
-      int n_pre = 0;
-      for (const Codec &k : xc.b2b) n_pre += k.at_start ? 1 : 0;
-      ZgShardLayoutArgs A{lpc, 0, cap, X, 4ull * n_pre, top.a2b.at_start ? 1u : 0u, xc.a2b.big_endian ? 1u : 0u};
-      HIPCHK(launch_shard_layout_var((uint32_t)items.size(), d_nf, d_items, d_ist, A, d_sh, d_off, d_index_ptr, d_len,
+      HIPCHK(launch_shard_layout_var((uint32_t)items.size(), T.nf, d_items, d_ist, T.A, T.dst, T.off, T.index_ptr, T.len,
                                      d_shst, (uint32_t)nS, s));
-      uint64_t lo = 4ull * n_pre, len = lpc * 16;
-      for (const Codec &k : xc.b2b) {
-        HIPCHK(launch_crc32c_encode(d_index_ptr, (uint32_t)nS, lo, len, k.at_start ? 1 : 0, s));
-        if (k.at_start) lo -= 4;
-        len += 4;
-      }
+      checksums_in_place(T.index_ptr, (uint32_t)nS, *EL.index, s);
       uint64_t *h_len = sc.pinned<uint64_t>(2 * nS);
-      HIPCHK(hipMemcpyAsync(h_len, d_len, nS * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(h_len, T.len, nS * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(hipMemcpyAsync(h_len + nS, d_shst, nS * 4, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       for (uint64_t i = 0; i < nS; i++)
