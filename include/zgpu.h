@@ -74,6 +74,17 @@ extern "C" {
  *  ZGPU_HIP_ERROR              -> device runtime failure (no zarrs equivalent)
  *  ZGPU_STORAGE_ERROR          -> StorageError::IOError from the filesystem store (open/read
  *                                 failures other than a missing key; zarrs_storage/src/lib.rs)
+ *  ZGPU_CAST_NOT_REPRESENTABLE -> CodecError::Other from CastValueError::NotRepresentable ("scalar is
+ *                                 not representable in target data type", zarrs_data_type/src/
+ *                                 codec_traits/cast_value.rs): a cast_value chain met an element it
+ *                                 cannot cast. Decode: the status of every descriptor whose SELECTION
+ *                                 holds such an element (as zarrs' partial decoder, which casts only the
+ *                                 selection); that descriptor's region of the output is unspecified,
+ *                                 the call's other descriptors decode as usual, and a descriptor that
+ *                                 already failed below the cast keeps that status. Encode and store:
+ *                                 the entries have no per-chunk status, so the call fails, returns
+ *                                 nothing, and zgpu_last_error names the first flat element index of
+ *                                 the array (zarrs would fail only that chunk's store).
  */
 enum {
   ZGPU_OK = 0,
@@ -89,6 +100,7 @@ enum {
   ZGPU_INVALID_ARGUMENT = 10,
   ZGPU_HIP_ERROR = 11,
   ZGPU_STORAGE_ERROR = 12,
+  ZGPU_CAST_NOT_REPRESENTABLE = 13,
 };
 
 /* decode flags */
@@ -137,7 +149,19 @@ const char *zgpu_version(void);
  *                crc32c (+numcodecs.crc32c), numcodecs.adler32 (location start, the default, or
  *                end), numcodecs.fletcher32, gzip, numcodecs.zlib, numcodecs.bz2 (decode only),
  *                zstd, numcodecs.shuffle, blosc (blosclz, lz4, lz4hc, zlib, snappy, zstd; shuffle /
- *                bitshuffle). Others -> ZGPU_UNSUPPORTED.
+ *                bitshuffle); the value codecs numcodecs.fixedscaleoffset, bitround and cast_value
+ *                and (unsharded) packbits. Others -> ZGPU_UNSUPPORTED.
+ *                cast_value ({"data_type", "rounding"?, "out_of_range"?, "scalar_map"?}, no other
+ *                field) casts between any two of int8..int64, uint8..uint64, float16, bfloat16,
+ *                float32, float64, bit-exact with zarrs: rounding nearest-even (default) /
+ *                towards-zero / towards-positive / towards-negative / nearest-away, out_of_range
+ *                absent / clamp / wrap (wrap with a float data_type: ZGPU_UNSUPPORTED), scalar_map
+ *                {encode?, decode?} of up to 32 [key, value] pairs per direction (more:
+ *                ZGPU_UNSUPPORTED), compared by the element's bits before the cast. Other data types
+ *                (int2/4, uint2/4, float8 and the other micro-floats, bool, complex) and a
+ *                configuration without data_type are ZGPU_UNSUPPORTED; a fill value that cannot be
+ *                cast, or that does not decode back to itself, is ZGPU_INVALID_ARGUMENT. An element
+ *                that cannot be cast: ZGPU_CAST_NOT_REPRESENTABLE (above).
  *                numcodecs.bz2 ({"level": 0..9}, required, no other field) reads the first bzip2
  *                stream of a chunk and ignores what follows it; the block CRCs and the combined
  *                CRC are checked whatever validate_checksums says, and a truncated, malformed or

@@ -18,6 +18,7 @@ pub const ZGPU_SHUFFLE_LENGTH: c_int = 9;
 pub const ZGPU_INVALID_ARGUMENT: c_int = 10;
 pub const ZGPU_HIP_ERROR: c_int = 11;
 pub const ZGPU_STORAGE_ERROR: c_int = 12;
+pub const ZGPU_CAST_NOT_REPRESENTABLE: c_int = 13;
 
 pub const ZGPU_ENC_DEVICE: u32 = 0x1;
 pub const ZGPU_OUT_DEVICE: u32 = 0x2;

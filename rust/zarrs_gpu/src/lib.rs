@@ -20,8 +20,10 @@
 //! * [`ArrayGpuExt`] adds a batched `retrieve_array_subset` for arrays of any supported chain
 //!   (unsharded C2/C5-style arrays): all intersecting chunks go to the GPU in one
 //!   `zgpu_retrieve_array_subset` call (Array::retrieve_array_subset_into,
-//!   array_read_ops_common.rs:20-179). Chains with `numcodecs.fixedscaleoffset`, `bitround` or
-//!   (unsharded) `packbits` are accepted there and by the sharding plugin's inner chains.
+//!   array_read_ops_common.rs:20-179). Chains with `numcodecs.fixedscaleoffset`, `bitround`,
+//!   `cast_value` or (unsharded) `packbits` are accepted there and by the sharding plugin's inner
+//!   chains; `ZGPU_CAST_NOT_REPRESENTABLE` is `CodecError::Other` from
+//!   `CastValueError::NotRepresentable`.
 //!
 //! Status codes map onto `CodecError` variants as include/zgpu.h documents.
 //!
@@ -411,6 +413,10 @@ pub(crate) fn status_error(status: c_int) -> CodecError {
         ffi::ZGPU_SHUFFLE_LENGTH => CodecError::Other(
             "the shuffle codec expects the input byte length to be an integer multiple of the elementsize".into(),
         ),
+        ffi::ZGPU_CAST_NOT_REPRESENTABLE => {
+            // CastValueError::NotRepresentable through cast_bytes (cast_value_codec.rs)
+            CodecError::Other("scalar is not representable in target data type".into())
+        }
         _ => {
             // SAFETY: zgpu_status_name returns a static string.
             let name = unsafe { CStr::from_ptr(ffi::zgpu_status_name(status)) }.to_string_lossy();

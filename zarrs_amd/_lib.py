@@ -16,11 +16,11 @@ MAX_DIMS = 8
 STATUS_NAMES = [
     "OK", "INVALID_CHECKSUM", "DECODED_SIZE_MISMATCH", "SHARD_INDEX_OOB", "CORRUPT_STREAM",
     "INVALID_BYTE_RANGE", "UNSUPPORTED", "CRC_INPUT_TOO_SHORT", "SHARD_TOO_SMALL", "SHUFFLE_LENGTH",
-    "INVALID_ARGUMENT", "HIP_ERROR", "STORAGE_ERROR",
+    "INVALID_ARGUMENT", "HIP_ERROR", "STORAGE_ERROR", "CAST_NOT_REPRESENTABLE",
 ]
 OK, INVALID_CHECKSUM, DECODED_SIZE_MISMATCH, SHARD_INDEX_OOB, CORRUPT_STREAM, INVALID_BYTE_RANGE, \
     UNSUPPORTED, CRC_INPUT_TOO_SHORT, SHARD_TOO_SMALL, SHUFFLE_LENGTH, INVALID_ARGUMENT, HIP_ERROR, \
-    STORAGE_ERROR = range(13)
+    STORAGE_ERROR, CAST_NOT_REPRESENTABLE = range(14)
 
 ENC_DEVICE = 0x1
 OUT_DEVICE = 0x2

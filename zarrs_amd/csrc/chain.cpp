@@ -1,10 +1,11 @@
 // Codec chain parsing (see chain.hpp). Reference: codec_chain.rs:192-229 (from_metadata: exactly one
 // array->bytes codec, error otherwise), zarrs_codec/src/lib.rs:372-449 (name -> codec lookup), and the
 // per-codec configurations in zarrs_metadata_ext/src/codec/registered/{transpose,bytes,sharding,
-// crc32c,gzip,zstd,shuffle}.rs, zarrs_metadata_ext/src/codec/numcodecs/{zlib,adler32,fletcher32,bz2}.rs
+// crc32c,gzip,zstd,shuffle,cast_value}.rs, zarrs_metadata_ext/src/codec/numcodecs/{zlib,adler32,fletcher32,bz2}.rs
 // (created by zarrs/src/array/codec/bytes_to_bytes/{zlib,adler32,fletcher32,bz2}.rs).
 #include "chain.hpp"
 
+#include <cerrno>
 #include <cstring>
 
 #include "../../include/zgpu.h"
@@ -117,6 +118,151 @@ void bitround_element(uint32_t vt, uint32_t keepbits, uint8_t *elem) {
   }
 }
 
+// ---- cast_value -----------------------------------------------------------------------------------
+static_assert((uint32_t)VT_I8 == CT_I8 && (uint32_t)VT_I64 == CT_I64 && (uint32_t)VT_U8 == CT_U8 &&
+                  (uint32_t)VT_U64 == CT_U64 && (uint32_t)VT_F32 == CT_F32 && (uint32_t)VT_F64 == CT_F64 &&
+                  (uint32_t)VT_F16 == CT_F16 && (uint32_t)VT_BF16 == CT_BF16 && (uint32_t)VT_NONE == CT_COUNT,
+              "kernels/cast.hpp numbers the element types as ZgValueType");
+
+bool cast_decode_fallible(const Codec &k) { return !cast_infallible(k.vt_enc, k.vt_dec, k.cast_oor); }
+bool cast_encode_fallible(const Codec &k) { return !cast_infallible(k.vt_dec, k.vt_enc, k.cast_oor); }
+
+// One scalar_map key or value as DataType::fill_value_v3 reads it for the 12 cast_value types
+// (zarrs/src/array/data_type/macros.rs @fill_value, zarrs_metadata/src/v3/array/fill_value.rs as_*):
+// the integers take a JSON integer within the type's range (as_i64 / as_u64, then try_from); the floats a
+// JSON number (read as f64, then rounded to nearest even), "NaN" (the canonical pattern), "Infinity",
+// "-Infinity", or "0x" and the element's bits as big-endian hex digits. Returns the element's bits.
+static uint64_t cast_scalar(const Json &v, uint32_t vt, const std::string &dt) {
+  const ChainError bad{ZGPU_INVALID_ARGUMENT, "cast_value: scalar_map entry is not a valid " + dt + " value"};
+  const uint32_t size = value_type_size(vt);
+  if (!cast_type_is_float(vt)) {
+    if (v.kind != Json::Num || !v.is_int) throw bad;
+    const char *tok = v.s.c_str();
+    char *end = nullptr;
+    errno = 0;
+    if (cast_type_is_signed(vt)) {
+      const long long x = std::strtoll(tok, &end, 10);
+      if (errno || *end) throw bad;
+      const int64_t lo = size == 8 ? INT64_MIN : -((int64_t)1 << (8 * size - 1));
+      if (x < lo || x > -(lo + 1)) throw bad;
+      return size == 8 ? (uint64_t)x : (uint64_t)x & (((uint64_t)1 << (8 * size)) - 1);
+    }
+    if (tok[0] == '-') throw bad;
+    const unsigned long long x = std::strtoull(tok, &end, 10);
+    if (errno || *end) throw bad;
+    if (size < 8 && x >> (8 * size)) throw bad;
+    return x;
+  }
+  uint64_t bits = 0;
+  auto from_double = [&](double d) {
+    const CastMap none{};
+    uint8_t out[8] = {0};
+    cast_elements_host(VT_F64, vt, (const uint8_t *)&d, out, 1, none, CAST_NEAREST_EVEN, CAST_OOR_CLAMP);  // overflow: inf
+    std::memcpy(&bits, out, size);
+  };
+  if (v.kind == Json::Num) {
+    from_double(v.num);
+  } else if (v.kind == Json::Str) {
+    if (v.s == "NaN") from_double(std::numeric_limits<double>::quiet_NaN());
+    else if (v.s == "Infinity") from_double(std::numeric_limits<double>::infinity());
+    else if (v.s == "-Infinity") from_double(-std::numeric_limits<double>::infinity());
+    else if (v.s.size() == 2 + 2 * (size_t)size && v.s.compare(0, 2, "0x") == 0) {
+      for (size_t i = 2; i < v.s.size(); i++) {
+        const char c = v.s[i];
+        const int h = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+        if (h < 0) throw bad;
+        bits = (bits << 4) | (uint64_t)h;
+      }
+    } else {
+      throw bad;
+    }
+  } else {
+    throw bad;
+  }
+  return bits;
+}
+
+// build_scalar_map (cast_value_codec.rs:353-373): [[key, value], ...] with keys of type `from` and values
+// of type `to`. Every entry is kept, in order: the lookup takes the first match, as or_insert does.
+static void cast_scalar_map(const Json *list, uint32_t from, const std::string &from_dt, uint32_t to,
+                            const std::string &to_dt, CastMap &map) {
+  if (!list || list->kind == Json::Null) return;
+  if (list->kind != Json::Arr) throw ChainError{ZGPU_INVALID_ARGUMENT, "cast_value: scalar_map lists must be arrays"};
+  if (list->arr.size() > CAST_MAP_MAX)
+    throw ChainError{ZGPU_UNSUPPORTED, "cast_value: more than " + std::to_string(CAST_MAP_MAX) +
+                                           " scalar_map entries in one direction are not supported by the GPU pipeline"};
+  for (const Json &e : list->arr) {
+    if (e.kind != Json::Arr || e.arr.size() != 2)
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "cast_value: a scalar_map entry must be [key, value]"};
+    map.key[map.n] = cast_scalar(e.arr[0], from, from_dt);
+    map.val[map.n] = cast_scalar(e.arr[1], to, to_dt);
+    map.n++;
+  }
+}
+
+static void cast_encode_element(const Codec &k, const uint8_t *in, uint8_t *out, bool decode, bool &ok) {
+  ok = decode ? cast_elements_host(k.vt_enc, k.vt_dec, in, out, 1, k.cast_dec_map, k.cast_rounding, k.cast_oor) == 1
+              : cast_elements_host(k.vt_dec, k.vt_enc, in, out, 1, k.cast_enc_map, k.cast_rounding, k.cast_oor) == 1;
+}
+
+// CastValueCodecConfigurationV1 (registered/cast_value.rs:22-37, deny_unknown_fields) and with_context
+// (cast_value_codec.rs:112-191)
+static void create_cast_value(Codec &k, const Json *cfg, TypeCtx &T) {
+  k.kind = CodecKind::CastValue;
+  const Json *d = cfg && cfg->kind == Json::Obj ? cfg->get("data_type") : nullptr;
+  if (!d)  // the only configuration variant is V1, which has data_type (new_with_configuration's wording)
+    throw ChainError{ZGPU_UNSUPPORTED, "this cast_value codec configuration variant is unsupported"};
+  for (const auto &kv : cfg->obj)
+    if (kv.first != "data_type" && kv.first != "rounding" && kv.first != "out_of_range" && kv.first != "scalar_map")
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "cast_value: unknown field '" + kv.first + "'"};
+  std::string target;
+  if (d->kind == Json::Str) target = d->s;
+  else if (d->kind == Json::Obj && d->get("name") && d->get("name")->kind == Json::Str) target = d->get("name")->s;
+  else throw ChainError{ZGPU_INVALID_ARGUMENT, "cast_value: data_type must be a name or {name, configuration}"};
+  auto pick = [&](const char *key, std::initializer_list<const char *> names, uint32_t absent) -> uint32_t {
+    const Json *v = cfg->get(key);
+    if (!v || v->kind == Json::Null) return absent;
+    uint32_t i = 0;
+    for (const char *n : names) {
+      if (v->kind == Json::Str && v->s == n) return i;
+      i++;
+    }
+    throw ChainError{ZGPU_INVALID_ARGUMENT, std::string("cast_value: bad ") + key};
+  };
+  k.cast_rounding = pick("rounding", {"nearest-even", "towards-zero", "towards-positive", "towards-negative", "nearest-away"},
+                         CAST_NEAREST_EVEN);
+  const uint32_t oor = pick("out_of_range", {"clamp", "wrap"}, UINT32_MAX);
+  k.cast_oor = oor == UINT32_MAX ? (uint32_t)CAST_OOR_NONE : oor + 1;
+  // codec_castvalue(): the data types with the cast_value trait that this pipeline takes
+  k.vt_dec = value_type_of(T.dt);
+  k.vt_enc = value_type_of(target);
+  if (k.vt_enc == VT_NONE) throw ChainError{ZGPU_UNSUPPORTED, "cast_value: data_type " + target};
+  if (k.vt_dec == VT_NONE) throw ChainError{ZGPU_UNSUPPORTED, "cast_value: on data type " + T.dt};
+  if (k.cast_oor == CAST_OOR_WRAP && cast_type_is_float(k.vt_enc))  // validate_wrap_mode: UnsupportedDataType
+    throw ChainError{ZGPU_UNSUPPORTED, "cast_value: out_of_range=wrap needs an integer data_type, not " + target};
+  if (const Json *sm = cfg->get("scalar_map")) {
+    if (sm->kind != Json::Obj && sm->kind != Json::Null)
+      throw ChainError{ZGPU_INVALID_ARGUMENT, "cast_value: scalar_map must be {encode?, decode?}"};
+    if (sm->kind == Json::Obj) {
+      for (const auto &kv : sm->obj)
+        if (kv.first != "encode" && kv.first != "decode")
+          throw ChainError{ZGPU_INVALID_ARGUMENT, "cast_value: scalar_map: unknown field '" + kv.first + "'"};
+      cast_scalar_map(sm->get("encode"), k.vt_dec, T.dt, k.vt_enc, target, k.cast_enc_map);
+      cast_scalar_map(sm->get("decode"), k.vt_enc, target, k.vt_dec, T.dt, k.cast_dec_map);
+    }
+  }
+  uint8_t ef[16] = {0}, back[16] = {0};
+  bool ok = true;
+  cast_encode_element(k, T.fill, ef, false, ok);
+  if (!ok) throw ChainError{ZGPU_INVALID_ARGUMENT, "cast_value: the fill value is not representable in " + target};
+  cast_encode_element(k, ef, back, true, ok);
+  if (!ok || std::memcmp(back, T.fill, T.es) != 0)
+    throw ChainError{ZGPU_INVALID_ARGUMENT, "cast_value fill value does not survive a round-trip cast"};
+  std::memcpy(T.fill, ef, 16);
+  T.dt = target;
+  data_type_info(target, T.es, T.comp);
+}
+
 bool chain_has_value_codec(const Chain &c) {
   for (const Codec &k : c.a2a)
     if (is_value_codec(k.kind)) return true;
@@ -132,7 +278,7 @@ uint64_t packbits_size(const Codec &k, uint64_t nelem) {
 // bound before the array->bytes codec wherever they stand in the list).
 static bool a2a_name(const std::string &n) {
   return n == "transpose" || n == "numcodecs.fixedscaleoffset" || n == "bitround" || n == "numcodecs.bitround" ||
-         n == "https://codec.zarrs.dev/array_to_bytes/bitround";
+         n == "https://codec.zarrs.dev/array_to_bytes/bitround" || n == "cast_value";
 }
 
 // Codec names zarrs itself creates (zarrs/src/array/codec/**: impl_extension_aliases! v3 names and
@@ -140,7 +286,7 @@ static bool a2a_name(const std::string &n) {
 // "must_understand": false, so it is an error here rather than a skip (skipping would decode wrongly).
 static bool zarrs_knows(const std::string &n) {
   static const char *names[] = {
-      "cast_value", "reshape",    "zarrs.squeeze", "numcodecs.pcodec", "zfp",       "zarrs.zfp",      "numcodecs.zfpy",
+      "reshape",    "zarrs.squeeze", "numcodecs.pcodec", "zfp",       "zarrs.zfp",      "numcodecs.zfpy",
       "zarrs.vlen", "zarrs.vlen_v2", "vlen-bytes", "vlen-utf8",        "vlen-array", "zarrs.optional", "zarrs.gdeflate"};
   for (const char *k : names)
     if (n == k) return true;
@@ -217,6 +363,10 @@ static Role create_codec(Codec &k, const Json *cfg, TypeCtx &T) {
     k.vt_dec = k.vt_enc = value_type_of(dt);
     if (k.vt_dec == VT_NONE) throw ChainError{ZGPU_UNSUPPORTED, "bitround: data type " + dt};
     bitround_element(k.vt_dec, k.keepbits, T.fill);
+    return Role::A2A;
+  }
+  if (k.name == "cast_value") {
+    create_cast_value(k, cfg, T);
     return Role::A2A;
   }
   if (k.name == "packbits") {

@@ -9,11 +9,12 @@
 #include <vector>
 
 #include "json.hpp"
+#include "kernels/cast.hpp"
 
 namespace zgpu {
 
 enum class CodecKind { Transpose, Bytes, Sharding, Crc32c, Gzip, Zstd, Shuffle, Blosc, Zlib, Adler32, Fletcher32, Bz2,
-                       PackBits, FixedScaleOffset, BitRound };
+                       PackBits, FixedScaleOffset, BitRound, CastValue };
 
 struct Chain;
 
@@ -42,6 +43,10 @@ struct Codec {
   uint32_t vt_dec = 0, vt_enc = 0;  // ZgValueType
   bool fso_astype = false;
   uint32_t keepbits = 0;
+  // cast_value: vt_dec -> vt_enc on encode and back on decode, both with the same rounding (CastRounding)
+  // and out_of_range (CastOutOfRange), each direction through its own scalar map
+  uint32_t cast_rounding = 0, cast_oor = 0;
+  CastMap cast_enc_map{}, cast_dec_map{};
 };
 
 // Element types of the value codecs (the kernels' template parameter).
@@ -49,7 +54,9 @@ enum ZgValueType : uint32_t { VT_I8, VT_I16, VT_I32, VT_I64, VT_U8, VT_U16, VT_U
                               VT_F16, VT_BF16, VT_NONE };
 ZgValueType value_type_of(const std::string &data_type);
 
-inline bool is_value_codec(CodecKind k) { return k == CodecKind::FixedScaleOffset || k == CodecKind::BitRound; }
+inline bool is_value_codec(CodecKind k) {
+  return k == CodecKind::FixedScaleOffset || k == CodecKind::BitRound || k == CodecKind::CastValue;
+}
 
 struct Chain {
   std::vector<Codec> a2a;
@@ -73,6 +80,9 @@ uint64_t packbits_size(const Codec &k, uint64_t nelem);
 // kernels/value.hip compute the same): out receives the encoded element.
 void fso_encode_element(const Codec &k, const uint8_t *in, uint8_t *out);
 void bitround_element(uint32_t vt, uint32_t keepbits, uint8_t *elem);
+// Whether a cast_value codec's decode (encode) can meet an element it cannot cast (cast_infallible).
+bool cast_decode_fallible(const Codec &k);
+bool cast_encode_fallible(const Codec &k);
 uint32_t value_type_size(uint32_t vt);
 
 struct ChainError {

@@ -503,40 +503,51 @@ static uint32_t mantissa_bits_of(uint32_t vt) {
   return vt == VT_F16 ? 10 : vt == VT_BF16 ? 7 : vt == VT_F32 ? 23 : vt == VT_F64 ? 52 : 0;
 }
 
+// Whether a value codec's decode changes the elements (bitround's is the identity).
+static bool decode_converts(const Codec &k) {
+  return k.kind == CodecKind::FixedScaleOffset || k.kind == CodecKind::CastValue;
+}
+
 // n elements through the value codecs' decode (`steps` in encode order, run backwards) from `in`, in
 // the innermost encoded type, into `out` (must not be `in`), in the decoded type. bitround decodes
-// as the identity. Temporaries go to `sc`. Enqueues only.
+// as the identity. A cast_value step lowers *fail (device, preset to ~0; null when no step can fail) to
+// the index of an element it cannot cast. Temporaries go to `sc`. Enqueues only.
 static void value_decode_elements(const std::vector<Codec> &steps, const uint8_t *in, uint8_t *out, uint64_t n,
-                                  uint32_t es_out, Scratch &sc, hipStream_t s) {
-  std::vector<const Codec *> fso;
+                                  uint32_t es_out, Scratch &sc, hipStream_t s, uint64_t *fail) {
+  std::vector<const Codec *> conv;
   for (size_t j = steps.size(); j-- > 0;)
-    if (steps[j].kind == CodecKind::FixedScaleOffset) fso.push_back(&steps[j]);
-  if (fso.empty()) {
+    if (decode_converts(steps[j])) conv.push_back(&steps[j]);
+  if (conv.empty()) {
     if (n) HIPCHK(hipMemcpyAsync(out, in, n * es_out, hipMemcpyDeviceToDevice, s));
     return;
   }
   const uint8_t *cur = in;
-  for (size_t j = 0; j < fso.size(); j++) {
-    const Codec &k = *fso[j];
+  for (size_t j = 0; j < conv.size(); j++) {
+    const Codec &k = *conv[j];
     uint8_t *dst = out;
-    if (j + 1 < fso.size()) {
+    if (j + 1 < conv.size()) {
       dst = sc.dev<uint8_t>(std::max<uint64_t>(n * value_type_size(k.vt_dec), 1));
     }
-    HIPCHK(launch_fso_decode(k.vt_enc, k.vt_dec, cur, dst, n, k.fso_offset, k.fso_scale, k.fso_astype ? 1 : 0, s));
+    if (k.kind == CodecKind::CastValue)
+      HIPCHK(launch_cast(k.vt_enc, k.vt_dec, cur, dst, n, k.cast_rounding, k.cast_oor, k.cast_dec_map, fail, s));
+    else
+      HIPCHK(launch_fso_decode(k.vt_enc, k.vt_dec, cur, dst, n, k.fso_offset, k.fso_scale, k.fso_astype ? 1 : 0, s));
     cur = dst;
   }
 }
 
 // n elements through the value codecs' encode, `in` (decoded type) to a new device array in the
-// innermost encoded type (returned, in `sc`).
+// innermost encoded type (returned, in `sc`). fail: as for value_decode_elements, for the encode casts.
 uint8_t *value_encode_elements(const std::vector<Codec> &steps, const uint8_t *in, uint64_t n, Scratch &sc,
-                               hipStream_t s) {
+                               hipStream_t s, uint64_t *fail) {
   const uint8_t *cur = in;
   uint8_t *dst = nullptr;
   for (const Codec &k : steps) {
     dst = sc.dev<uint8_t>(std::max<uint64_t>(n * value_type_size(k.vt_enc), 1));
     if (k.kind == CodecKind::FixedScaleOffset)
       HIPCHK(launch_fso_encode(k.vt_dec, k.vt_enc, cur, dst, n, k.fso_offset, k.fso_scale, k.fso_astype ? 1 : 0, s));
+    else if (k.kind == CodecKind::CastValue)
+      HIPCHK(launch_cast(k.vt_dec, k.vt_enc, cur, dst, n, k.cast_rounding, k.cast_oor, k.cast_enc_map, fail, s));
     else
       HIPCHK(launch_bitround(value_type_size(k.vt_dec), mantissa_bits_of(k.vt_dec), k.keepbits, cur, dst, n, s));
     cur = dst;
@@ -547,10 +558,16 @@ uint8_t *value_encode_elements(const std::vector<Codec> &steps, const uint8_t *i
 // Chains with value codecs, before sharding_indexed, inside its inner chains, or both. The chain
 // without them, retyped to the innermost encoded data type and fill value, decodes the callers'
 // selections into a device buffer of that type (so a missing chunk or inner chunk holds the encoded
-// fill value, as in zarrs); k_fso_decode then converts the buffer into the output: one extra pass over
-// the data when the descriptors cover the output (the converted buffer is the output), and through the
-// stacked boxes of transposed_general otherwise. Only bitround: its decode is the identity, so the
+// fill value, as in zarrs); k_fso_decode / k_cast then convert the buffer into the output: one extra pass
+// over the data when the descriptors cover the output (the converted buffer is the output), and through
+// the stacked boxes of transposed_general otherwise. Only bitround: its decode is the identity, so the
 // stripped chain writes the output itself.
+// A cast_value decode that can meet an element it cannot cast (cast_decode_fallible) always takes the
+// stacked boxes, which are contiguous and hold only the selected elements: every box is converted by
+// launches of its own with its own failure word, read back once, and a descriptor whose box failed gets
+// ZGPU_CAST_NOT_REPRESENTABLE (zarrs' partial decoder casts the selection, so only it counts) while the
+// others are scattered as usual. A descriptor that failed in the stripped chain has no box and keeps
+// that status.
 static void value_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, const zgpu_chunk_desc *descs,
                           uint64_t n, int32_t *status) {
   const Chain &top = *chain;
@@ -558,9 +575,12 @@ static void value_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, c
   std::vector<Codec> steps;
   auto bare = strip_value_codecs(top, steps);
   retype_stripped(*bare, top);
-  bool any_fso = false;
-  for (const Codec &k : steps) any_fso = any_fso || k.kind == CodecKind::FixedScaleOffset;
-  if (!any_fso) {
+  bool converts = false, fallible = false;
+  for (const Codec &k : steps) {
+    converts = converts || decode_converts(k);
+    fallible = fallible || (k.kind == CodecKind::CastValue && cast_decode_fallible(k));
+  }
+  if (!converts) {
     decode_general(G, bare, descs, n, status);
     return;
   }
@@ -573,12 +593,12 @@ static void value_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, c
     covered += sel_volume(descs[i], nd);
   }
   for (uint32_t d = 0; d < nd; d++) out_elems *= G.out_shape[d];
-  if (geometry && covered == out_elems) {
+  if (geometry && covered == out_elems && !fallible) {
     // the (disjoint) selections tile the output: decode into its image in the encoded type, convert
     uint8_t *T = sc.dev<uint8_t>(std::max<uint64_t>(out_elems * es_e, 1));
     GeneralCall G1{G.C, G.validate, nd, T, G.out_shape, G.flags, G.s, {}};
     decode_general(G1, bare, descs, n, status);
-    value_decode_elements(steps, T, G.out, out_elems, es_d, sc, G.s);
+    value_decode_elements(steps, T, G.out, out_elems, es_d, sc, G.s, nullptr);
     return;
   }
   // every selection into its own box of a stacked buffer, packed compact, converted, then scattered
@@ -611,8 +631,32 @@ static void value_general(GeneralCall &G, const std::shared_ptr<Chain> &chain, c
     B.leaf[j].enc = PkD + B.elem_off[j] * es_d;
     B.leaf[j].enc_len = B.leaf[j].enc_len / es_e * es_d;
   }
-  value_decode_elements(steps, B.pk, PkD, B.elems, es_d, sc, G.s);
-  run_sub(G, plain, B.leaf, B.owner, status);
+  if (!fallible) {
+    value_decode_elements(steps, B.pk, PkD, B.elems, es_d, sc, G.s, nullptr);
+    run_sub(G, plain, B.leaf, B.owner, status);
+    return;
+  }
+  const size_t nb = B.leaf.size();
+  if (!nb) return;
+  uint64_t *d_fail = sc.dev<uint64_t>(nb);
+  HIPCHK(hipMemsetAsync(d_fail, 0xff, nb * 8, G.s));
+  for (size_t j = 0; j < nb; j++)
+    value_decode_elements(steps, B.pk + B.elem_off[j] * es_e, PkD + B.elem_off[j] * es_d, B.leaf[j].enc_len / es_d, es_d,
+                          sc, G.s, d_fail + j);
+  std::vector<uint64_t> failed(nb);
+  HIPCHK(hipMemcpyAsync(failed.data(), d_fail, nb * 8, hipMemcpyDeviceToHost, G.s));
+  HIPCHK(hipStreamSynchronize(G.s));
+  std::vector<zgpu_chunk_desc> cast_leaf;
+  std::vector<uint64_t> cast_owner;
+  for (size_t j = 0; j < nb; j++) {
+    if (failed[j] != UINT64_MAX) {
+      status[B.owner[j]] = ZGPU_CAST_NOT_REPRESENTABLE;
+      continue;
+    }
+    cast_leaf.push_back(B.leaf[j]);
+    cast_owner.push_back(B.owner[j]);
+  }
+  run_sub(G, plain, cast_leaf, cast_owner, status);
 }
 
 // packbits as the array->bytes codec (unsharded): its chunks are not element-aligned, so whole chunks

@@ -137,6 +137,7 @@ struct Json {
       j.kind = Num;
       j.num = std::strtod(tok.c_str(), nullptr);
       j.is_int = integral;
+      j.s = tok;  // the digits as written: an integer past int64 is read from them (chain.cpp, cast_value)
       if (integral) j.i = std::strtoll(tok.c_str(), nullptr, 10);
     }
     return j;

@@ -282,6 +282,13 @@ hipError_t launch_fso_decode(uint32_t vt_enc, uint32_t vt_dec, const void *in, v
                              float scale, int through_f32, hipStream_t s);
 hipError_t launch_fso_encode(uint32_t vt_dec, uint32_t vt_enc, const void *in, void *out, uint64_t n, float offset,
                              float scale, int through_f32, hipStream_t s);
+// cast_value, n elements of ZgValueType vt_src to vt_dst (any of the 12, float16 and bfloat16 included)
+// through `map` (the direction's scalar map) and cast_one (kernels/cast.hpp). rounding: CastRounding;
+// oor: CastOutOfRange. An element that cannot be cast writes 0 and lowers *fail (a device word the caller
+// presets to ~0; may be null when the direction cannot fail) to its index. in != out.
+struct CastMap;
+hipError_t launch_cast(uint32_t vt_src, uint32_t vt_dst, const void *in, void *out, uint64_t n, uint32_t rounding,
+                       uint32_t oor, const CastMap &map, uint64_t *fail, hipStream_t s);
 // bitround encode of n elements of `width` bytes (1, 2, 4, 8); mant: the float type's mantissa bits,
 // 0 for integers
 hipError_t launch_bitround(uint32_t width, uint32_t mant, uint32_t keepbits, const void *in, void *out, uint64_t n,

@@ -1,7 +1,7 @@
-// The codecs that change element values or widths: numcodecs.fixedscaleoffset and bitround (array->
-// array, per element) and packbits (array->bytes, not element-aligned). Element semantics are in
-// value.hpp, shared with the host; the reference is fixedscaleoffset_codec.rs:159-380, zarrs_data_type/
-// src/codec_traits/bitround.rs:3-45 and packbits_codec.rs:216-400.
+// The codecs that change element values or widths: numcodecs.fixedscaleoffset, bitround and cast_value
+// (array->array, per element) and packbits (array->bytes, not element-aligned). Element semantics are in
+// value.hpp and cast.hpp, shared with the host; the reference is fixedscaleoffset_codec.rs:159-380,
+// zarrs_data_type/src/codec_traits/bitround.rs:3-45, codec_traits/cast_value.rs and packbits_codec.rs:216-400.
 //
 // Floating point in k_fso_decode / k_fso_encode has to match Rust bit for bit. How the build holds
 // each property (the Makefile gives this file its own flags on top of the common ones):
@@ -25,6 +25,7 @@
 
 #include "../chain.hpp"
 #include "../common.hpp"
+#include "cast.hpp"
 #include "launch.hpp"
 #include "value.hpp"
 
@@ -80,6 +81,42 @@ __global__ __launch_bounds__(256) void k_bitround(const U *__restrict__ in, U *_
   map_elements<U, U>(in, out, n, vec, [=](U x) { return bitround_one<U>(x, keepbits, mant); });
 }
 
+// cast_value, S -> T (decode is k_cast<T, S> with the decode map): the scalar map, then cast_one
+// (cast.hpp), over the same vector shape as map_elements. rounding, out_of_range and the map are uniform
+// kernel arguments. An element that cannot be cast writes 0; every thread keeps the smallest index it
+// met and ends with one atomicMin on *fail (the host presets it to ~0), so an infallible pair, whose
+// `ok` the compiler sees constant, has neither the compare nor the atomic.
+template <class S, class T>
+__global__ __launch_bounds__(256) void k_cast(const S *__restrict__ in, T *__restrict__ out, uint64_t n,
+                                              uint32_t rounding, uint32_t oor, CastMap map,
+                                              unsigned long long *__restrict__ fail, int vec) {
+  constexpr int V = 16 / (sizeof(S) > sizeof(T) ? sizeof(S) : sizeof(T));
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (uint64_t)gridDim.x * blockDim.x;
+  unsigned long long bad = ~0ull;
+  auto one = [&](S x, uint64_t idx) {
+    bool ok = true;
+    const T y = cast_mapped<S, T>(x, map, rounding, oor, ok);
+    if (!ok && idx < bad) bad = idx;
+    return y;
+  };
+  uint64_t done = 0;
+  if (vec) {
+    const uint64_t groups = n / V;
+    const ZgVec<S, V> *vi = reinterpret_cast<const ZgVec<S, V> *>(in);
+    ZgVec<T, V> *vo = reinterpret_cast<ZgVec<T, V> *>(out);
+    for (uint64_t g = tid; g < groups; g += nth) {
+      const ZgVec<S, V> a = vi[g];
+      ZgVec<T, V> r;
+#pragma unroll
+      for (int k = 0; k < V; k++) r.v[k] = one(a.v[k], g * V + k);
+      vo[g] = r;
+    }
+    done = groups * V;
+  }
+  for (uint64_t j = done + tid; j < n; j += nth) out[j] = one(in[j], j);
+  if (bad != ~0ull && fail) atomicMin(fail, bad);
+}
+
 static uint32_t map_grid(uint64_t n, uint32_t per_thread) {
   const uint64_t want = (n / per_thread + 255) / 256 + 1;
   const uint64_t cap = (uint64_t)device_cu_count() * 8;
@@ -132,6 +169,21 @@ hipError_t launch_fso_encode(uint32_t vt_dec, uint32_t vt_enc, const void *in, v
       constexpr uint32_t V = 16 / (sizeof(E) > sizeof(T) ? sizeof(E) : sizeof(T));
       hipLaunchKernelGGL((k_fso_encode<T, E>), dim3(map_grid(n, V)), dim3(256), 0, s, (const T *)in, (E *)out, n, offset,
                          scale, through_f32, both_aligned(in, out));
+    });
+  }) && ok;
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+hipError_t launch_cast(uint32_t vt_src, uint32_t vt_dst, const void *in, void *out, uint64_t n, uint32_t rounding,
+                       uint32_t oor, const CastMap &map, uint64_t *fail, hipStream_t s) {
+  if (!n) return hipSuccess;
+  bool ok = with_cast_type(vt_src, [&](auto a) {
+    using S = decltype(a);
+    ok = with_cast_type(vt_dst, [&](auto b) {
+      using T = decltype(b);
+      constexpr uint32_t V = 16 / (sizeof(S) > sizeof(T) ? sizeof(S) : sizeof(T));
+      hipLaunchKernelGGL((k_cast<S, T>), dim3(map_grid(n, V)), dim3(256), 0, s, (const S *)in, (T *)out, n, rounding, oor,
+                         map, (unsigned long long *)fail, both_aligned(in, out));
     });
   }) && ok;
   return ok ? hipGetLastError() : hipErrorInvalidValue;

@@ -222,7 +222,7 @@ uint64_t sel_volume(const zgpu_chunk_desc &D, uint32_t nd);
 std::shared_ptr<Chain> strip_value_codecs(const Chain &c, std::vector<Codec> &steps);
 void retype_stripped(Chain &c, const Chain &original);
 uint8_t *value_encode_elements(const std::vector<Codec> &steps, const uint8_t *in, uint64_t n, Scratch &sc,
-                               hipStream_t s);
+                               hipStream_t s, uint64_t *fail);
 // write.cpp: zgpu_encode_chunks (arguments checked) on stream s, synchronous; fixed_only: refuse a chain
 // whose chunks vary in length (zgpu_encode_batch)
 int encode_chunks_on(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, const void *array,

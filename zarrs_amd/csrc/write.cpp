@@ -360,7 +360,26 @@ int encode_chunks_on(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, c
   if (fixed_only && !L.fixed)
     return set_err(ZGPU_INVALID_ARGUMENT, "encode: the chain's chunks have variable lengths: zgpu_encode_chunks");
   if (const int rc = check_destinations(descs, n, L.size)) return rc;
-  if (stripped) array = value_encode_elements(steps, (const uint8_t *)array, volume(array_shape, nd), sc, s);
+  if (stripped) {
+    // the encode entries carry no per-chunk status: an element cast_value cannot cast fails the call
+    const Codec *fallible = nullptr;
+    for (const Codec &k : steps)
+      if (k.kind == CodecKind::CastValue && cast_encode_fallible(k)) fallible = &k;
+    uint64_t *d_fail = nullptr;
+    if (fallible) {
+      d_fail = sc.dev<uint64_t>(1);
+      HIPCHK(hipMemsetAsync(d_fail, 0xff, 8, s));
+    }
+    array = value_encode_elements(steps, (const uint8_t *)array, volume(array_shape, nd), sc, s, d_fail);
+    if (fallible) {
+      uint64_t first = UINT64_MAX;
+      HIPCHK(hipMemcpyAsync(&first, d_fail, 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      if (first != UINT64_MAX)
+        return set_err(ZGPU_CAST_NOT_REPRESENTABLE, "encode: cast_value: element " + std::to_string(first) +
+                                                        " of the array is not representable in the encoded data type");
+    }
+  }
   if (L.path == ENC_FIXED) return encode_plain(L, nd, chunk_shape, array, array_shape, descs, n, enc_lens, sc, s);
   uint64_t *hl = sc.pinned<uint64_t>(n);  // the variable lengths, read back by the callee
   const int rc = L.path == ENC_PACKBITS ? encode_packbits(L, nd, chunk_shape, array, array_shape, descs, n, hl, sc, s)

@@ -143,8 +143,8 @@ const char *zgpu_status_name(int s) {
   static const char *names[] = {"OK", "INVALID_CHECKSUM", "DECODED_SIZE_MISMATCH", "SHARD_INDEX_OOB",
                                 "CORRUPT_STREAM", "INVALID_BYTE_RANGE", "UNSUPPORTED", "CRC_INPUT_TOO_SHORT",
                                 "SHARD_TOO_SMALL", "SHUFFLE_LENGTH", "INVALID_ARGUMENT", "HIP_ERROR",
-                                "STORAGE_ERROR"};
-  return (s >= 0 && s <= 12) ? names[s] : "UNKNOWN";
+                                "STORAGE_ERROR", "CAST_NOT_REPRESENTABLE"};
+  return (s >= 0 && s <= 13) ? names[s] : "UNKNOWN";
 }
 
 const char *zgpu_last_error(const zgpu_ctx *) { return g_last_error.c_str(); }
