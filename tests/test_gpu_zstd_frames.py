@@ -119,3 +119,19 @@ def test_lone_chain_takes_the_latency_mode_by_default(chunk, k, monkeypatch):
     assert st == [0]
     assert _where(c[0], got[0]) is None, _where(c[0], got[0])
     assert ctr["zstd_latency"] == 1 and ctr["zstd_parallel"] == 1 and ctr["zstd_serial"] == 0, ctr
+
+
+@pytest.mark.parametrize("path", list(PATHS))
+def test_skippable_frames_alone_decode_to_nothing(path, monkeypatch):
+    """An input of skippable frames only holds no data: ZSTD_decompress returns 0 bytes and no error
+    (test_zstd_frames_model.py), so zarrs' zstd codec hands `bytes` nothing (zstd_codec.rs:119-123) and the
+    chunk fails with the size error, not as a corrupt stream. In front of a frame they are passed over."""
+    from types import SimpleNamespace
+    from zarrs_amd import _lib as L
+    for enc in (Z.skippable(), Z.skippable() + Z.skippable(b"", 7)):
+        st, _, _ = _decode([SimpleNamespace(enc=enc, expect=bytes(16))], False, PATHS[path], monkeypatch)
+        assert st[0] == L.DECODED_SIZE_MISMATCH, st
+    data = bytes(range(16))
+    st, got, _ = _decode([SimpleNamespace(enc=Z.skippable() + Z.stream_frame(data, 0), expect=data)], False, PATHS[path],
+                         monkeypatch)
+    assert st == [0] and got[0].tobytes() == data

@@ -57,3 +57,10 @@ def test_streaming_shapes_named_in_the_builder():
     assert Z.blocks(f)[-1] == (Z.RAW, 0) and Z.zstd_decompress(f, 300) == b"abc" * 100
     assert Z.stream_frame(b"x" * 1000, 100, pledged=False)[4] >> 5 == 0  # no FCS field, not single-segment
     assert Z.stream_frame(b"x" * 1000, 100, pledged=True)[4] & 0x20
+
+
+def test_libzstd_decodes_no_frame_to_nothing():
+    """no bytes, and skippable frames alone: 0 bytes and no error (what the GPU decoder must hand on)"""
+    assert Z.zstd_decompress(b"", 16) == b""
+    assert Z.zstd_decompress(Z.skippable(), 16) == b""
+    assert Z.zstd_decompress(Z.skippable() + Z.skippable(b"", 7), 16) == b""

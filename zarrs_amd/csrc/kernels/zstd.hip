@@ -742,7 +742,6 @@ __device__ __attribute__((noinline)) void zstd_serial_item(ZSmem &S, uint32_t it
   uint8_t *lit = lit_scratch + (uint64_t)item * lit_stride;
   uint32_t err = 0;
   uint64_t ip = 0;
-  bool any_frame = false;
 #define ZFAIL(code)   \
   {                   \
     err = (code);     \
@@ -760,7 +759,6 @@ __device__ __attribute__((noinline)) void zstd_serial_item(ZSmem &S, uint32_t it
     }
     if (magic != 0xFD2FB528u) ZFAIL(ZG_CORRUPT_STREAM);
     ip += 4;
-    any_frame = true;
     const uint32_t fhd = I.b(ip++);
     const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, has_ck = (fhd >> 2) & 1, did_flag = fhd & 3;
     if (fhd & 8) ZFAIL(ZG_CORRUPT_STREAM);  // reserved bit
@@ -1109,7 +1107,8 @@ __device__ __attribute__((noinline)) void zstd_serial_item(ZSmem &S, uint32_t it
     }
   }
 #undef ZFAIL
-  if (!err && !any_frame) err = ZG_CORRUPT_STREAM;
+  // no frame at all (no bytes, or skippable frames only) decodes to nothing, as ZSTD_decompress does
+  // (zstd_codec.rs:119-123): the next codec, not this one, finds the length wrong
   if (!err) out_flush(S, O);
   if (lane == 0) {
     if (err) {
@@ -1742,7 +1741,7 @@ __global__ __launch_bounds__(64) void k_zstd_scan(const ZgItem *items, uint32_t 
       }
     }
   }
-  if (!err && !serial && !any_frame) err = ZG_CORRUPT_STREAM;
+  if (!err && !serial && !any_frame) serial = true;  // no frame: zero bytes, by the serial decoder
   __syncthreads();
   // ---- (D) the records, one lane per block ----
   if (!serial && !err) {
