@@ -121,6 +121,24 @@ def test_lone_chain_takes_the_latency_mode_by_default(chunk, k, monkeypatch):
     assert ctr["zstd_latency"] == 1 and ctr["zstd_parallel"] == 1 and ctr["zstd_serial"] == 0, ctr
 
 
+def test_default_executor_changes_where_the_batch_fills_the_device(monkeypatch):
+    """With no ZGPU_ZSTD_* variable set, the latency mode takes a batch while n_items * 3 < 4 * CUs
+    (DESIGN.md, the launch policy's table) and no batch past that: lo = (4 * CUs - 1) // 3 frames of one
+    4 KiB chain all finish there, lo + 1 frames all finish in the block-parallel pipeline without it (341
+    and 342 on 256 CUs)."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    lo = (4 * cus - 1) // 3
+    c = [c for c in Z.family_chains_exact() if c.name == "depth_4096_k17"]
+    assert len(c) == 1 and c[0].parallel is True
+    for n, lat in ((lo, lo), (lo + 1, 0)):
+        st, got, ctr = _decode(c * n, False, {}, monkeypatch)
+        print(cus, "CUs,", n, "frames: counters", ctr)
+        assert st == [0] * n
+        assert (got == np.frombuffer(c[0].expect, np.uint8)).all()
+        assert ctr["zstd_latency"] == lat and ctr["zstd_parallel"] == n and ctr["zstd_serial"] == 0, ctr
+
+
 @pytest.mark.parametrize("path", list(PATHS))
 def test_skippable_frames_alone_decode_to_nothing(path, monkeypatch):
     """An input of skippable frames only holds no data: ZSTD_decompress returns 0 bytes and no error

@@ -443,8 +443,9 @@ HUF_TAB = (1 << 12) * 2 + 16  # zstd.hip: a Huffman decoding table in the litera
 
 
 def layout(chunk: int):
-    """(blk_cap, lit_stride, seq_cap) of a chunk of `chunk` decoded bytes: zstd_scratch_layout
-    (zarrs_amd/csrc/kernels/zstd.hip) over the plan's slot (the chunk rounded up to 256 bytes)."""
+    """(blk_cap, lit_stride, seq_cap) of a chunk of `chunk` decoded bytes: zstd_scratch_sizes
+    (zarrs_amd/csrc/zstd_launch.cpp; tests/test_zstd_launch.py holds the two together) over the plan's
+    slot (the chunk rounded up to 256 bytes)."""
     slot = (chunk + 255) & ~255
     lit_stride = (max(slot + slot // 8, BLOCK_MAX + 64 + 2 * HUF_TAB) + 255) & ~255
     return min(slot // 32768 + 64, 1 << 20), lit_stride, slot // 4 + 1024

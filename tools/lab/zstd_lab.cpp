@@ -15,6 +15,7 @@
 
 #include "common.hpp"
 #include "kernels/zstd.hip"
+#include "zstd_launch.cpp"  // (the launch policy: the lab links no libzgpu)
 
 typedef struct ZSTD_CCtx_s ZSTD_CCtx;
 extern "C" {
@@ -140,19 +141,34 @@ int main(int argc, char **argv) {
   uint32_t *d_status;
   CK(hipMalloc(&d_items, n * sizeof(ZgItem)));
   CK(hipMalloc(&d_status, n * 4));
+  int ncu = 256;
+  CK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
+  // the library's scratch sizes and launch policy; LAB_EXEC=par: the latency mode forced, whatever the batch
+  const bool lab_par = getenv("LAB_EXEC") && !strcmp(getenv("LAB_EXEC"), "par");
+  zgpu::ZstdKnobs knobs;
+  knobs.xwin = lab_par ? 1 : -1;
+  const zgpu::ZstdScratchSizes SZ = zgpu::zstd_scratch_sizes(n, chunk, ncu, zgpu::ZstdWants{false, lab_par, knobs});
+  zgpu::ZstdCaps caps;
+  caps.ext = SZ.ext != 0;
+  caps.lit_rec_wgs = SZ.lit_rec_wgs;
+  const zgpu::ZstdLaunch PL = zgpu::zstd_launch_policy(n, chunk, ncu, caps, knobs);
+  if (lab_par && PL.executor != zgpu::ZstdExecutor::LATENCY) {
+    printf("LAB_EXEC=par: %d chunks of %llu bytes are past the latency mode's batch limit\n", n, (unsigned long long)chunk);
+    return 2;
+  }
   zgpu::ZstdScratch Z{};
-  uint64_t blk_bytes;
-  zgpu::zstd_scratch_layout(chunk, Z.blk_cap, blk_bytes, Z.lit_stride, Z.seq_cap);
-  CK(hipMalloc(&Z.blks, n * (uint64_t)Z.blk_cap * blk_bytes));
-  CK(hipMalloc(&Z.nblk, n * 4));
-  CK(hipMalloc(&Z.mode, n * 4));
-  CK(hipMalloc(&Z.lit, n * Z.lit_stride));
-  CK(hipMalloc(&Z.seq, n * Z.seq_cap * 12));
-  if (!getenv("LAB_NONORM")) CK(hipMalloc(&Z.norm, n * (uint64_t)Z.blk_cap * zgpu::zstd_norm_bytes()));
-  if (getenv("LAB_EXEC") && !strcmp(getenv("LAB_EXEC"), "par")) {
-    CK(hipMalloc(&Z.ext, 2 * (uint64_t)n * chunk * 4));
-    CK(hipMalloc(&Z.ext_cnt, zgpu::ZEXT_ROUNDS * 8));
-    Z.ext_items = n;
+  Z.blk_cap = SZ.blk_cap;
+  Z.lit_stride = SZ.lit_stride;
+  Z.seq_cap = SZ.seq_cap;
+  CK(hipMalloc(&Z.blks, SZ.blks));
+  CK(hipMalloc(&Z.nblk, SZ.nblk));
+  CK(hipMalloc(&Z.mode, SZ.mode));
+  CK(hipMalloc(&Z.lit, SZ.lit));
+  CK(hipMalloc(&Z.seq, SZ.seq));
+  if (!getenv("LAB_NONORM")) CK(hipMalloc(&Z.norm, SZ.norm));
+  if (SZ.ext) {
+    CK(hipMalloc(&Z.ext, SZ.ext));
+    CK(hipMalloc(&Z.ext_cnt, SZ.ext_cnt));
   }
 
   constexpr int NK = 7;
@@ -186,24 +202,15 @@ int main(int argc, char **argv) {
     CK(hipMemcpyToSymbol(HIP_SYMBOL(zgpu::g_litstats), z, sizeof(z)));
   }
 #endif
-  int ncu = 256;
-  CK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
   const int reps = getenv("LAB_REPS") ? atoi(getenv("LAB_REPS")) : 3;
   uint8_t *lit_rec = nullptr;  // literal record slots (LAB_NOREC=1: none)
-  {
-    uint32_t wgs = 0;
-    const uint64_t rb = zgpu::zstd_lit_rec_bytes(wgs);
-    if (rb && !getenv("LAB_NOREC") && wgs >= (uint32_t)ncu * ZG_LIT_GRID_PER_CU) CK(hipMalloc(&lit_rec, rb));
-  }
+  if (PL.rec_slots && !getenv("LAB_NOREC")) CK(hipMalloc(&lit_rec, SZ.lit_rec));
   for (int rep = 0; rep < reps; rep++) {
     CK(hipMemcpy(d_items, items.data(), n * sizeof(ZgItem), hipMemcpyHostToDevice));
     CK(hipMemset(d_status, 0, n * 4));
     CK(hipMemset(d_out, 0xA5, (size_t)n * chunk));
     zgpu::ZBlk *blks = (zgpu::ZBlk *)Z.blks;
-    const uint64_t recs = (uint64_t)n * Z.blk_cap;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(recs, (uint64_t)ncu * 16);
-    const uint32_t lgrid = (uint32_t)std::min<uint64_t>(recs, (uint64_t)ncu * ZG_LIT_GRID_PER_CU);
-    const uint32_t bgrid = (uint32_t)std::min<uint64_t>(recs, std::max<uint64_t>(grid, (uint64_t)ncu * 4 * ZG_BLK_WPE));
+    const uint32_t grid = PL.grid, lgrid = PL.lgrid, bgrid = PL.bgrid;
     CK(hipEventRecord(ev[0]));
     hipLaunchKernelGGL(zgpu::k_zstd_scan, dim3(n), dim3(64), 0, 0, d_items, d_status, blks, Z.blk_cap, Z.nblk, Z.mode,
                        Z.lit_stride, Z.seq_cap, 0u, (unsigned long long *)nullptr, (uint32_t *)nullptr,
@@ -230,15 +237,14 @@ int main(int argc, char **argv) {
                        Z.mode, (uint32_t)n, d_out, chunk, Z.lit, Z.lit_stride, (const uint64_t *)nullptr,
                        (const unsigned long long *)nullptr, 0);
     CK(hipEventRecord(ev[6]));
-    if (xk == 3) {  // the latency mode, as launch_zstd_pass runs it
+    if (xk == 3) {  // the latency mode, as launch_zstd runs it
       const uint64_t tot = (uint64_t)n * chunk;
       CK(hipMemsetAsync(Z.ext, 0xFF, tot * 4, 0));
       CK(hipMemsetAsync(Z.ext_cnt, 0, zgpu::ZEXT_ROUNDS * 8, 0));
-      hipLaunchKernelGGL(zgpu::k_zstd_exec_win<true>, dim3(ncu), dim3(zgpu::xwin::THREADS), 0, 0, d_items, d_status,
+      hipLaunchKernelGGL(zgpu::k_zstd_exec_win<true>, dim3(PL.persist_grid), dim3(zgpu::xwin::THREADS), 0, 0, d_items, d_status,
                          blks, Z.blk_cap, Z.nblk, Z.mode, d_out, chunk, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap,
                          (uint32_t)n, Z.ext, (const unsigned long long *)nullptr);
-      const uint32_t rounds = zgpu::zstd_ext_rounds(Z.blk_cap, chunk);
-      const uint32_t g2 = (uint32_t)std::min<uint64_t>((tot / 4 + 255) / 256, (uint64_t)ncu * 16);
+      const uint32_t rounds = PL.rounds, g2 = PL.round_grid;
       uint32_t *ea = Z.ext, *eb = Z.ext + tot;
       for (uint32_t r = 0; r < rounds; r++) {
         hipLaunchKernelGGL(zgpu::k_zstd_ext_round, dim3(g2), dim3(256), 0, 0, ea, eb, d_out, chunk, tot,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../common.hpp"
+#include "../zstd_launch.hpp"
 
 #include <cstdlib>
 
@@ -116,8 +117,8 @@ struct ZstdScratch {
   uint32_t *seq;         // n_items * seq_cap sequences of 3 u32
   uint64_t seq_cap;
   uint32_t blk_cap;
-  int16_t *norm = nullptr;  // n_items * blk_cap * zstd_norm_bytes(): FSE counts the scan parsed (nullable)
-  uint32_t force_serial = 0;               // every item on the serial one-wave decoder (tests, ZGPU_ZSTD_FORCE_SERIAL)
+  int16_t *norm = nullptr;  // n_items * blk_cap * ZNORM: FSE counts the scan parsed (nullable)
+  ZstdKnobs knobs{};        // the environment's switches, as read for this execution
   unsigned long long *counters = nullptr;  // [serial-fallback items, block-parallel items] (nullable)
   // compacted serial-fallback items (nullable: the fallback then runs one wave per item): k_zstd_scan
   // appends them, the fallback is a small persistent grid over the list, launched only when
@@ -132,8 +133,7 @@ struct ZstdScratch {
   // one stream only: Huffman literals before the sequences (ZGPU_ZSTD_LITS_FIRST; the literal decoder
   // then writes literal-only blocks to the scratch, as k_zstd_plan has not placed them yet)
   uint32_t lits_first = 0;
-  // literal record slots (k_zstd_lits pass 1 keeps its symbols; nullable: every lane decodes twice):
-  // zstd_lit_rec_bytes() bytes for lit_rec_wgs workgroups
+  // literal record slots of lit_rec_wgs workgroups (k_zstd_lits pass 1 keeps its symbols; nullable: all decode twice)
   uint8_t *lit_rec = nullptr;
   uint32_t lit_rec_wgs = 0;
   // Block aliases (nullable; the blosc stage sets it: its consumer k_blosc_finish reads the decoded
@@ -143,34 +143,17 @@ struct ZstdScratch {
   // k_zstd_direct does not copy it into the slot: item bytes [off, off + len) are src[0 .. len).
   // len = 0: none. Byte-shuffled blosc blocks of noisy data: the low-byte plane is a raw block.
   uint64_t *alias = nullptr;
-  // Two halves (nullable s2: one pass): the second half of the items runs on stream s2, its entropy
-  // kernels after the first half's (ev_half), beside the first half's executor; the caller's stream
-  // waits for ev_done. Both halves share the side stream and the literal record slots (their literal
-  // kernels never overlap).
-  hipStream_t s2 = nullptr;
-  hipEvent_t ev_half = nullptr, ev_done = nullptr;
   // the batch's largest block count per item (nullable; zeroed before the call, k_zstd_scan's
   // atomicMax): the record-strided kernels walk n_items x that many records, not x blk_cap
   unsigned long long *max_nblk = nullptr;
-  // Latency mode of the window executor (nullable: off): two ext arrays of ext_items * slot u32 each
+  // Latency mode of the window executor (nullable: off): two ext arrays of n_items * slot u32 each
   // (the external references of k_zstd_exec_win<true>) and ZEXT_ROUNDS round counters
   uint32_t *ext = nullptr;
   unsigned long long *ext_cnt = nullptr;
-  uint64_t ext_items = 0;
   unsigned long long *lat_count = nullptr;  // items the latency mode finished (nullable)
 };
-constexpr uint32_t ZALIAS = 2;
-// latency mode: batches of at most this many decoded bytes (n_items x slot) get the ext arrays
-constexpr uint64_t ZPAR_MAX_BYTES = 128ull << 20;
-constexpr uint32_t ZEXT_ROUNDS = 24;
-// rounds of k_zstd_ext_round for items of blk_cap block records and slot_bytes decoded bytes
-uint32_t zstd_ext_rounds(uint32_t blk_cap, uint64_t slot_bytes);
 constexpr uint64_t ZALIAS_RLE = 1ull << 63;
-uint64_t zstd_lit_rec_bytes(uint32_t &wgs);
-// bytes of FSE-count scratch per block record (ZstdScratch::norm)
-uint64_t zstd_norm_bytes();
-void zstd_scratch_layout(uint64_t slot_bytes, uint32_t &blk_cap, uint64_t &blk_bytes, uint64_t &lit_stride,
-                         uint64_t &seq_cap);
+// sized by zstd_scratch_sizes, launched as zstd_launch_policy decides (../zstd_launch.hpp)
 hipError_t launch_zstd(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst, uint64_t slot_bytes,
                        const ZstdScratch &Z, hipStream_t s);
 // standalone unshuffle (when shuffle is not directly above the bytes codec)

@@ -24,8 +24,6 @@
 #include "launch.hpp"
 #include "xxh.hpp"
 
-#include <cstdlib>
-
 namespace zgpu {
 
 #ifdef ZG_PROFILE
@@ -57,11 +55,6 @@ namespace {
 constexpr int ZRING = 16384, ZRMASK = ZRING - 1;
 constexpr int ZBATCH = 4096;         // max output span of one sequence batch
 constexpr uint32_t ZBIG = 2048;      // sequences with a longer run are executed alone, chunked
-constexpr uint32_t BLOCK_MAX = 131072;
-constexpr uint32_t MAX_HUF_LOG = 12;
-// a block's Huffman decoding table in the literal scratch, right before its literals: 2^12 u16
-// entries + a 16-B header holding the table log (0: invalid description)
-constexpr uint32_t HUF_TAB = (1u << MAX_HUF_LOG) * 2 + 16;
 // per-item decode mode chosen by k_zstd_scan
 constexpr uint32_t ZMODE_PARALLEL = 0, ZMODE_SERIAL = 1, ZMODE_SKIP = 2;
 
@@ -1164,9 +1157,6 @@ namespace {
 constexpr uint32_t ZB_RAW = 0, ZB_RLE = 1, ZB_CMP = 2;
 constexpr uint32_t ZBF_FIRST = 1u << 8, ZBF_LAST = 1u << 9, ZBF_FCS = 1u << 10, ZBF_CK = 1u << 11;
 constexpr uint32_t ZSYM = 0x80000000u;      // symbolic offset: ZSYM | slot << 24 | minus
-// normalized-count scratch: per block record 3 tables x 64 int16 (counts of symbols 0..52; [62] the
-// accuracy log, [63] the symbol count)
-constexpr uint32_t ZNORM = 3 * 64;
 
 struct ZBlk {
   uint32_t flags;             // bits 0-1 block type, 2-3 literal type, 4 four streams, ZBF_*
@@ -1196,14 +1186,12 @@ struct ZBlk {
   uint64_t in_src;            // record 0: the item's encoded bytes (k_zstd_plan; the executor's
                               // last segment rewrites the item record while others may still start)
 };
+static_assert(sizeof(ZBlk) == ZBLK_BYTES, "zstd_params.hpp restates the block record's size");
 
 struct ZScanSmem {
   int16_t norm[64];
 };
 
-#ifndef ZG_BLK_WPE
-#define ZG_BLK_WPE 6  // waves per SIMD k_zstd_blocks is compiled for
-#endif
 // 4-byte sequence decoding entry: bits 0-8 next state base, 9-12 state bits, 13-17 value extra bits,
 // 18-23 code (LL/ML: index of its value base; OF: the offset code itself, value base 1 << code), bit
 // 31 a code outside the format. Everything the bit stream's order depends on (state and extra bit
@@ -2066,14 +2054,10 @@ constexpr uint32_t LIT_LDS = ZG_LIT_LDS;
 #define ZG_LIT_WARM 128
 #endif
 constexpr int32_t LIT_WARM = ZG_LIT_WARM;
-constexpr uint32_t LIT_THREADS = 256;
 #ifndef ZG_LIT_WPE
 #define ZG_LIT_WPE 4  // min waves per SIMD k_zstd_lits is compiled for (4: 100 VGPRs, no spills, with staging)
 #endif
 constexpr int LIT_STAGE_R = ZG_LIT_WPE >= 4 ? 4 : 8;  // 16-B staging loads in flight per thread
-#ifndef ZG_LIT_GRID_PER_CU
-#define ZG_LIT_GRID_PER_CU 4
-#endif
 #ifndef ZG_LIT_STAGE_W
 #define ZG_LIT_STAGE_W 32  // staging window bytes per lane: one 32-B sector (lab PMC: literal writes
                            // 2,994 -> 643 MB per launch on 64 C5 chunks, 1.2x the literal bytes)
@@ -2373,9 +2357,6 @@ __device__ __forceinline__ void hl_write_bf(HufLane &H, int32_t &p, int32_t stop
   L.finish();
 }
 
-// Record slot per lane: REC_OWN bytes of the lane's own chain (from its entry), then REC_RB bytes of
-// a repair's true-chain prefix. A lane whose symbols do not fit decodes again (pass 2) instead.
-constexpr uint32_t REC_OWN = 1024, REC_RB = 64, REC_SLOT = REC_OWN + REC_RB;
 static_assert(REC_OWN % 8 == 0 && REC_RB % 8 == 0, "record slot words");
 
 // Pass 1 with records: hl_count_bf's loop, each symbol also packed into 8-B words of the lane's slot
@@ -2772,7 +2753,7 @@ __device__ __forceinline__ bool x_direct_block(uint32_t flags, uint32_t nseq, ui
 }
 
 // A compressed block without sequences is its literals: when k_zstd_plan has run before the literal
-// decoder (one stream, no aliases: launch_zstd_pass), k_zstd_lits writes them straight into the slot
+// decoder (one stream, no aliases: launch_zstd), k_zstd_lits writes them straight into the slot
 // at the block's output offset and k_zstd_direct leaves the block alone - the literal scratch round
 // trip (written by the literal decoder, read and written again by the direct copy) was 17.7 GB of
 // C5's 149 GB per step. The predicate both kernels apply:
@@ -2915,17 +2896,6 @@ __global__ __launch_bounds__(LIT_THREADS) __attribute__((amdgpu_waves_per_eu(ZG_
 // Executor segments: an item's blocks are cut where no later match reaches back before the cut (and
 // not inside a checksummed frame); each segment gets its own k_zstd_exec_item wave. Byte-shuffled
 // images cut at their byte planes (tools/lab/zstd_taint.cpp: no match crosses the plane boundary).
-#ifndef ZG_XSEG
-#define ZG_XSEG 12
-#endif
-// executor segments per item of the wave executor (at most; ZGPU_ZSTD_XSEG overrides it for both
-// executors, ZGPU_ZSTD_XSEG_WIDE for this one). Round 5 measured 2, 3, 4 and 8 within 1 % with 3 best
-// (profiles/r05/r05xs_zstd_exec_segment_major_xcd_ab.txt); with round 6's faster sequence decoder
-// and the plan group the L0 executors end the C5 step, and more segments shorten them: C5 73.2 (3),
-// 72.5 (8), 70.8 (12), 71.3 (16), 103 (32) ms (profiles/r06/r06zfg_*); blosc-zstd's 2-block frames
-// cut into 2 at most either way
-constexpr uint32_t XSEG = ZG_XSEG;
-
 __global__ __launch_bounds__(64) void k_zstd_plan(const ZgItem *items, uint32_t *status, ZBlk *blks,
                                                   uint32_t blk_cap, const uint32_t *nblk, const uint32_t *zmode,
                                                   uint64_t slot_bytes, uint32_t xseg, uint64_t *alias,
@@ -3180,259 +3150,87 @@ namespace xdense {
 // resolved in parallel by pointer jumping in LDS; the default executor (ZGPU_ZSTD_XWIN=0: the wave
 // executors above)
 #include "zstd_xwin.inc"
-#ifndef ZG_XSEG_WIN
-#define ZG_XSEG_WIN 8
-#endif
-constexpr uint32_t XSEG_WIN = ZG_XSEG_WIN;  // executor segments per item (at most) for k_zstd_exec_win
-#ifndef ZG_XWIN_MAX_WPC
-#define ZG_XWIN_MAX_WPC 4
-#endif
-// executor grids of at least this many waves (items x segments) per CU take xdense
-#ifndef ZG_XDENSE_WPC
-#define ZG_XDENSE_WPC 64
-#endif
-constexpr uint32_t XDENSE_WAVES_PER_CU = ZG_XDENSE_WPC;
-// launch_zstd splits a batch into two pipelined halves (ZstdScratch::s2) from 2 x this many items
-constexpr uint32_t ZSPLIT_MIN = 1024;
 
-uint64_t zstd_lit_rec_bytes(uint32_t &wgs) {
-  static const uint64_t cap = [] {
-    const char *e = std::getenv("ZGPU_ZSTD_LGRID");
-    return e ? std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) : (uint64_t)device_cu_count() * ZG_LIT_GRID_PER_CU;
-  }();
-  static const bool on = [] {
-    const char *e = std::getenv("ZGPU_ZSTD_LIT_REC");
-    return !e || std::atoi(e) != 0;
-  }();
-  wgs = on ? (uint32_t)cap : 0u;
-  return on ? cap * LIT_THREADS * REC_SLOT : 0ull;
-}
-uint64_t zstd_norm_bytes() { return ZNORM * sizeof(int16_t); }
-void zstd_scratch_layout(uint64_t slot_bytes, uint32_t &blk_cap, uint64_t &blk_bytes, uint64_t &lit_stride,
-                         uint64_t &seq_cap) {
-  blk_cap = (uint32_t)std::min<uint64_t>(slot_bytes / 32768 + 64, 1u << 20);
-  blk_bytes = sizeof(ZBlk);
-  // literals (<= the decoded size) + one Huffman table per block (HUF_TAB per >= 64 KiB of output on
-  // typical frames; frames of many tiny Huffman blocks overflow it and take the serial decoder)
-  lit_stride = std::max<uint64_t>(slot_bytes + slot_bytes / 8, BLOCK_MAX + 64 + 2 * HUF_TAB);
-  lit_stride = (lit_stride + 255) & ~(uint64_t)255;
-  seq_cap = slot_bytes / 4 + 1024;  // sequences per item (each decodes >= 3 bytes; typical >= 8)
-}
-// Latency mode: the pointer-jumping rounds k_zstd_ext_round is launched for (tools/lab/zstd_lab.cpp runs
-// the same rule).
-// Every hop of a reference chain leaves its window for an earlier window of the item (a
-// cell is external only when its source lies before its window's start, exec_task), so a chain has
-// at most as many hops as the item has windows. A latency-mode window ends at (a) its block's end:
-// at most blk_cap of these; (b) the end of its workgroup's WSPAN range of the block: at most
-// slot / WSPAN; (c) the end of a full sequence table (T = 1024 sequences of >= 3 bytes each): such
-// a window starts either where the previous table ended, and then spans >= 3 T bytes (at most
-// slot / (3 T) of these), or at its workgroup's range start (at most one per range: slot / WSPAN
-// again). The W-cell limit never ends one: W > WSPAN. So
-//   hops <= blk_cap + 2 slot / WSPAN + slot / (3 T) + 1,
-// and pointer jumping resolves a chain of d hops in floor(log2 d) + 1 rounds (each round halves
-// it); ceil(log2 hops) + 1 rounds are launched, at most ZEXT_ROUNDS (the largest latency batch,
-// ZPAR_MAX_BYTES in one item, needs 17). A round after the last reference returns at once, and
-// k_zstd_par_finish reads the last round's count: an item with a reference left reports an error.
-uint32_t zstd_ext_rounds(uint32_t blk_cap, uint64_t slot_bytes) {
-  const uint64_t hops = (uint64_t)blk_cap + 2 * (slot_bytes / xwin::WSPAN) + slot_bytes / (3 * xwin::T) + 1;
-  uint32_t rounds = 1;
-  while (rounds < ZEXT_ROUNDS && (1ull << (rounds - 1)) < hops) rounds++;
-  return rounds;
-}
-// One pass of the block-parallel pipeline over n_items items on stream s; ev_entropy (nullable) is
-// recorded on s once the entropy kernels (and the side stream's sequence decode) are done.
-static hipError_t launch_zstd_pass(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst,
-                                   uint64_t slot_bytes, const ZstdScratch &Z, hipStream_t s, hipEvent_t ev_entropy) {
+// Enqueue the block-parallel pipeline over n_items items on stream s as the launch policy
+// (../zstd_launch.hpp) decides it from the batch, the device and what Z provides.
+hipError_t launch_zstd(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst, uint64_t slot_bytes,
+                       const ZstdScratch &Z, hipStream_t s) {
   if (!n_items) return hipSuccess;
+  // what Z provides: side, alias, lits_first, ext, lit_rec_wgs, ser_list, launch_serial
+  const ZstdCaps caps{Z.side && Z.ev_fork && Z.ev_join, Z.alias != nullptr, Z.lits_first != 0, Z.ext && Z.ext_cnt,
+                      Z.lit_rec ? Z.lit_rec_wgs : 0u, Z.ser_list && Z.ser_count, Z.launch_serial != 0};
+  const ZstdLaunch L = zstd_launch_policy(n_items, slot_bytes, device_cu_count(), caps, Z.knobs);
   ZBlk *blks = (ZBlk *)Z.blks;
-  const bool listed = Z.ser_list && Z.ser_count;
+  const bool listed = L.serial != ZstdSerial::PER_ITEM;
   hipLaunchKernelGGL(k_zstd_scan, dim3(n_items), dim3(64), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
-                     Z.lit_stride, Z.seq_cap, Z.force_serial, Z.counters, listed ? Z.ser_list : nullptr,
+                     Z.lit_stride, Z.seq_cap, Z.knobs.force_serial ? 1u : 0u, Z.counters, listed ? Z.ser_list : nullptr,
                      listed ? Z.ser_count : nullptr, Z.max_nblk, Z.norm);
-  const uint64_t recs = (uint64_t)n_items * Z.blk_cap;
-  // grids of the record-strided entropy kernels (overridable for tuning: ZGPU_ZSTD_GRID, ZGPU_ZSTD_LGRID)
-  static const uint64_t g_cap = [] {
-    const char *e = std::getenv("ZGPU_ZSTD_GRID");
-    return e ? std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) : (uint64_t)device_cu_count() * 16;
-  }();
-  static const uint64_t l_cap = [] {
-    const char *e = std::getenv("ZGPU_ZSTD_LGRID");
-    // one resident wave of workgroups: the device's CUs x ZG_LIT_GRID_PER_CU workgroups of 256 lanes each
-    return e ? std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) : (uint64_t)device_cu_count() * ZG_LIT_GRID_PER_CU;
-  }();
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(recs, g_cap);
-  const uint32_t lgrid = (uint32_t)std::min<uint64_t>(recs, l_cap);
-  // the sequence decoder reads only the scan's block records and writes its own fields of them (and
-  // the sequence scratch): with a side stream it runs beside the literal kernels
-  const bool fork = Z.side && Z.ev_fork && Z.ev_join;
-  hipStream_t sq = fork ? Z.side : s;
-  // literal-only blocks decoded straight into the slot (lits_in_slot): needs k_zstd_plan's output
-  // offsets before the literal decoder, i.e. the sequence decoder on the same stream, and no aliases
-  static const bool lit_direct_env = [] {
-    const char *e = std::getenv("ZGPU_ZSTD_LITDIRECT");
-    return !e || std::atoi(e) != 0;
-  }();
-  const bool lits_first = Z.lits_first && !fork;
-  const bool lit_direct = lit_direct_env && !fork && !Z.alias && !lits_first;
-  // executor segments per item: ZG_XSEG (ZGPU_ZSTD_XSEG: tuning)
-  static const uint32_t xseg_env = [] {
-    const char *e = std::getenv("ZGPU_ZSTD_XSEG");
-    return e ? (uint32_t)std::min<unsigned long>(64, std::max<unsigned long>(1, std::strtoul(e, nullptr, 10))) : 0u;
-  }();
-  // executor: the windowed workgroup executor for batches the wave executor would leave mostly idle
-  // (fewer than ZG_XWIN_MAX_WPC of its waves per CU: lone frames, per-chunk calls, C5's L1 and small
-  // levels); the wave executor for batches that fill the GPU with waves (C5's L0 halves, blosc-zstd),
-  // where the window executor's whole-CU workgroups measured slower beside the other lanes' entropy
-  // kernels (C5 100 vs 91-94 ms with it everywhere, profiles/r06/r06h_*). ZGPU_ZSTD_XWIN=0/1 forces
-  // one (read per call: tests run both).
-  const char *xw_s = std::getenv("ZGPU_ZSTD_XWIN");
-  const int xw_env = xw_s ? std::atoi(xw_s) : -1;
-  const char *xwpc_s = std::getenv("ZGPU_ZSTD_XWIN_WPC");  // the threshold's waves per CU (A/B)
-  const uint64_t xwpc = xwpc_s ? (uint64_t)std::atoi(xwpc_s) : ZG_XWIN_MAX_WPC;
-  // (the threshold counts 3 waves per item, round 5's segment count: C5's L1 and small levels take the
-  // window executor, its L0 halves the wave executor)
-  const bool xwin_on = xw_env >= 0 ? xw_env != 0 : (uint64_t)n_items * 3 < (uint64_t)device_cu_count() * xwpc;
-  static const uint32_t xseg_wide_env = [] {  // A/B: the wave executor's segments only
-    const char *e = std::getenv("ZGPU_ZSTD_XSEG_WIDE");
-    return e ? (uint32_t)std::min<unsigned long>(64, std::max<unsigned long>(1, std::strtoul(e, nullptr, 10))) : 0u;
-  }();
-  static const uint32_t xseg_win_env = [] {  // A/B: the window executor's segments only
-    const char *e = std::getenv("ZGPU_ZSTD_XSEG_WIN");
-    return e ? (uint32_t)std::min<unsigned long>(64, std::max<unsigned long>(1, std::strtoul(e, nullptr, 10))) : 0u;
-  }();
-  const uint32_t xseg = xseg_env               ? xseg_env
-                        : xwin_on              ? (xseg_win_env ? xseg_win_env : XSEG_WIN)
-                                               : (xseg_wide_env ? xseg_wide_env : XSEG);
-
-  if (fork) {
+  hipStream_t sq = L.fork ? Z.side : s;
+  if (L.fork) {
     hipError_t e = hipEventRecord(Z.ev_fork, s);
     if (e == hipSuccess) e = hipStreamWaitEvent(Z.side, Z.ev_fork, 0);
     if (e != hipSuccess) return e;
   }
-  // one resident wave of the sequence decoder: CUs x 4 SIMDs x ZG_BLK_WPE waves (ZGPU_ZSTD_BLK_WPE: fewer,
-  // leaving CU slots to concurrent plans' kernels; A/B)
-  static const uint64_t blk_wpe = [] {
-    const char *e = std::getenv("ZGPU_ZSTD_BLK_WPE");
-    const int v = e ? std::atoi(e) : 0;
-    return (uint64_t)(v > 0 && v <= ZG_BLK_WPE ? v : 0);
-  }();
-  const uint32_t bgrid = (uint32_t)std::min<uint64_t>(
-      recs, blk_wpe ? (uint64_t)device_cu_count() * 4 * blk_wpe
-                    : std::max<uint64_t>(g_cap, (uint64_t)device_cu_count() * 4 * ZG_BLK_WPE));
-  const char *xp_s = std::getenv("ZGPU_ZSTD_XPAR");
-  const bool par = xwin_on && Z.ext && Z.ext_cnt && n_items <= Z.ext_items && (!xp_s || std::atoi(xp_s) != 0);
   // sequence decoder: one wave per block (the split chain decoder: lab 64 L0 chunks 1.63 ms against 5.0
   // with four blocks per wave, one per lane; C5 82.0 -> 74.7 ms, profiles/r06/r06pqr_*)
   auto launch_seq = [&] {
-    hipLaunchKernelGGL(k_zstd_blocks, dim3(bgrid), dim3(64), 0, sq, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
+    hipLaunchKernelGGL(k_zstd_blocks, dim3(L.bgrid), dim3(64), 0, sq, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
                        n_items, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, Z.max_nblk, Z.norm);
   };
-  if (!lits_first) launch_seq();
-  if (fork) {
+  if (!L.lits_first) launch_seq();
+  if (L.fork) {
     hipError_t e = hipEventRecord(Z.ev_join, Z.side);
     if (e != hipSuccess) return e;
   }
-  if (lit_direct)  // output offsets first: the literal decoder writes literal-only blocks into the slot
+  if (L.lit_direct)  // output offsets first: the literal decoder writes literal-only blocks into the slot
     hipLaunchKernelGGL(k_zstd_plan, dim3(n_items), dim3(64), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
-                       slot_bytes, xseg, Z.alias, Z.lit, Z.lit_stride);
-  hipLaunchKernelGGL(k_zstd_huf, dim3(grid), dim3(64), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode, n_items,
+                       slot_bytes, L.xseg, Z.alias, Z.lit, Z.lit_stride);
+  hipLaunchKernelGGL(k_zstd_huf, dim3(L.grid), dim3(64), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode, n_items,
                      Z.lit, Z.lit_stride, Z.max_nblk);
-  // record slots: one per lane of the persistent grid (allocated for l_cap workgroups)
-  uint8_t *lit_rec = (Z.lit_rec && lgrid <= Z.lit_rec_wgs) ? Z.lit_rec : nullptr;
-  hipLaunchKernelGGL(k_zstd_lits, dim3(lgrid), dim3(LIT_THREADS), 0, s, items, status, blks, Z.blk_cap, Z.nblk,
-                     Z.mode, n_items, Z.lit, Z.lit_stride, lit_rec, Z.max_nblk, lit_direct ? dst : nullptr, slot_bytes);
-  if (lits_first) launch_seq();  // same stream: after the literal decoder
-  if (fork) {
+  hipLaunchKernelGGL(k_zstd_lits, dim3(L.lgrid), dim3(LIT_THREADS), 0, s, items, status, blks, Z.blk_cap, Z.nblk,
+                     Z.mode, n_items, Z.lit, Z.lit_stride, L.rec_slots ? Z.lit_rec : nullptr, Z.max_nblk,
+                     L.lit_direct ? dst : nullptr, slot_bytes);
+  if (L.lits_first) launch_seq();  // same stream: after the literal decoder
+  if (L.fork) {
     hipError_t e = hipStreamWaitEvent(s, Z.ev_join, 0);
     if (e != hipSuccess) return e;
   }
-  if (ev_entropy) {
-    hipError_t e = hipEventRecord(ev_entropy, s);
-    if (e != hipSuccess) return e;
-  }
-  if (!lit_direct)
+  if (!L.lit_direct)
     hipLaunchKernelGGL(k_zstd_plan, dim3(n_items), dim3(64), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
-                       slot_bytes, xseg, Z.alias, Z.lit, Z.lit_stride);
-  hipLaunchKernelGGL(k_zstd_direct, dim3(grid), dim3(256), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
-                     n_items, dst, slot_bytes, Z.lit, Z.lit_stride, Z.alias, Z.max_nblk, lit_direct ? 1 : 0);
-  // executor configuration: xdense when the grid has many waves per CU (ZGPU_ZSTD_XDENSE=0/1 forces one)
-  const char *xd_s = std::getenv("ZGPU_ZSTD_XDENSE");  // read per call (tests force both)
-  const int xd_env = xd_s ? std::atoi(xd_s) : -1;
-  const bool dense = xd_env >= 0 ? xd_env != 0
-                                 : (uint64_t)n_items * xseg >= (uint64_t)device_cu_count() * XDENSE_WAVES_PER_CU;
-  // latency mode (ZGPU_ZSTD_XPAR=0 off; read per call): batches the plan gave ext arrays
-  if (par) {
+                       slot_bytes, L.xseg, Z.alias, Z.lit, Z.lit_stride);
+  hipLaunchKernelGGL(k_zstd_direct, dim3(L.grid), dim3(256), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
+                     n_items, dst, slot_bytes, Z.lit, Z.lit_stride, Z.alias, Z.max_nblk, L.lit_direct ? 1 : 0);
+  if (L.executor == ZstdExecutor::LATENCY) {
     const uint64_t tot = (uint64_t)n_items * slot_bytes;
     hipError_t e = hipMemsetAsync(Z.ext, 0xFF, tot * 4, s);
     if (e == hipSuccess) e = hipMemsetAsync(Z.ext_cnt, 0, ZEXT_ROUNDS * 8, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_zstd_exec_win<true>, dim3(device_cu_count()), dim3(xwin::THREADS), 0, s, items, status,
-                       blks, Z.blk_cap, Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap,
-                       n_items, Z.ext, Z.max_nblk);
-    // rounds: from the bound on an item's windows (zstd_ext_rounds above)
-    const uint32_t rounds = zstd_ext_rounds(Z.blk_cap, slot_bytes);
-    const uint32_t g2 = (uint32_t)std::min<uint64_t>((tot / 4 + 255) / 256, (uint64_t)device_cu_count() * 16);
+    hipLaunchKernelGGL(k_zstd_exec_win<true>, dim3(L.persist_grid), dim3(xwin::THREADS), 0, s, items, status, blks,
+                       Z.blk_cap, Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, n_items, Z.ext,
+                       Z.max_nblk);
     uint32_t *ea = Z.ext, *eb = Z.ext + tot;
-    for (uint32_t r = 0; r < rounds; r++) {
-      hipLaunchKernelGGL(k_zstd_ext_round, dim3(g2), dim3(256), 0, s, ea, eb, dst, slot_bytes, tot,
+    for (uint32_t r = 0; r < L.rounds; r++) {
+      hipLaunchKernelGGL(k_zstd_ext_round, dim3(L.round_grid), dim3(256), 0, s, ea, eb, dst, slot_bytes, tot,
                          r ? Z.ext_cnt + r - 1 : (const unsigned long long *)nullptr, Z.ext_cnt + r);
       std::swap(ea, eb);
     }
     hipLaunchKernelGGL(k_zstd_par_finish, dim3(n_items), dim3(64), 0, s, items, status, blks, Z.blk_cap, Z.nblk, Z.mode,
-                       dst, slot_bytes, (const uint32_t *)ea, (const unsigned long long *)(Z.ext_cnt + rounds - 1),
+                       dst, slot_bytes, (const uint32_t *)ea, (const unsigned long long *)(Z.ext_cnt + L.rounds - 1),
                        Z.lat_count);
-  } else if (xwin_on)
-    hipLaunchKernelGGL(k_zstd_exec_win<false>, dim3(n_items * xseg), dim3(xwin::THREADS), 0, s, items, status, blks,
-                       Z.blk_cap, Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, xseg,
+  } else if (L.executor == ZstdExecutor::WINDOW)
+    hipLaunchKernelGGL(k_zstd_exec_win<false>, dim3(n_items * L.xseg), dim3(xwin::THREADS), 0, s, items, status, blks,
+                       Z.blk_cap, Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, L.xseg,
                        (uint32_t *)nullptr, (const unsigned long long *)nullptr);
-  else if (dense)
-    hipLaunchKernelGGL(xdense::k_zstd_exec_item, dim3(n_items * xseg), dim3(64), 0, s, items, status, blks, Z.blk_cap,
-                       Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, xseg);
+  else if (L.executor == ZstdExecutor::WAVE_DENSE)
+    hipLaunchKernelGGL(xdense::k_zstd_exec_item, dim3(n_items * L.xseg), dim3(64), 0, s, items, status, blks, Z.blk_cap,
+                       Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, L.xseg);
   else
-    hipLaunchKernelGGL(xwide::k_zstd_exec_item, dim3(n_items * xseg), dim3(64), 0, s, items, status, blks, Z.blk_cap,
-                       Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, xseg);
-  if (!listed) {
-    hipLaunchKernelGGL(k_zstd, dim3(n_items), dim3(64), 0, s, items, status, dst, slot_bytes, Z.lit, Z.lit_stride,
-                       Z.mode, nullptr, nullptr);
-  } else if (Z.launch_serial) {
-    // the compacted serial items: a persistent grid of at most 4 waves per CU
-    const uint32_t sgrid = (uint32_t)std::min<uint64_t>(n_items, (uint64_t)device_cu_count() * 4);
-    hipLaunchKernelGGL(k_zstd, dim3(sgrid), dim3(64), 0, s, items, status, dst, slot_bytes, Z.lit, Z.lit_stride,
-                       Z.mode, Z.ser_list, Z.ser_count);
-  }
+    hipLaunchKernelGGL(xwide::k_zstd_exec_item, dim3(n_items * L.xseg), dim3(64), 0, s, items, status, blks, Z.blk_cap,
+                       Z.nblk, Z.mode, dst, slot_bytes, Z.lit, Z.lit_stride, Z.seq, Z.seq_cap, L.xseg);
+  if (L.serial != ZstdSerial::NONE)
+    hipLaunchKernelGGL(k_zstd, dim3(L.serial_grid), dim3(64), 0, s, items, status, dst, slot_bytes, Z.lit, Z.lit_stride,
+                       Z.mode, listed ? Z.ser_list : nullptr, listed ? Z.ser_count : nullptr);
   return hipGetLastError();
-}
-
-hipError_t launch_zstd(ZgItem *items, uint32_t *status, uint32_t n_items, uint8_t *dst, uint64_t slot_bytes,
-                       const ZstdScratch &Z, hipStream_t s) {
-  // read per call (tests switch these knobs between calls): ZGPU_ZSTD_SPLIT_MIN splits small batches
-  const char *sm = std::getenv("ZGPU_ZSTD_SPLIT_MIN");
-  const uint32_t split_min = sm ? (uint32_t)std::max<unsigned long>(1, std::strtoul(sm, nullptr, 10)) : ZSPLIT_MIN;
-  if (!Z.s2 || !Z.ev_half || !Z.ev_done || n_items < 2 * split_min)
-    return launch_zstd_pass(items, status, n_items, dst, slot_bytes, Z, s, nullptr);
-  // Two halves (ZstdScratch::s2): the second half's entropy kernels start once the first half's are
-  // done, so they run beside the first half's executor; the caller's stream joins the second half.
-  const uint32_t h = n_items / 2;
-  ZstdScratch A = Z;
-  A.s2 = nullptr;
-  hipError_t e = launch_zstd_pass(items, status, h, dst, slot_bytes, A, s, Z.ev_half);
-  if (e != hipSuccess) return e;
-  ZstdScratch B = Z;
-  B.s2 = nullptr;
-  B.blks = (uint8_t *)Z.blks + (uint64_t)h * Z.blk_cap * sizeof(ZBlk);
-  B.nblk = Z.nblk + h;
-  B.mode = Z.mode + h;
-  B.lit = Z.lit + (uint64_t)h * Z.lit_stride;
-  B.seq = Z.seq + (uint64_t)h * Z.seq_cap * 3;
-  B.alias = Z.alias ? Z.alias + (uint64_t)h * 3 * ZALIAS : nullptr;
-  B.ser_list = nullptr;  // the second half's serial fallback runs unlisted (one wave per item)
-  B.ser_count = nullptr;
-  if ((e = hipStreamWaitEvent(Z.s2, Z.ev_half, 0)) != hipSuccess) return e;
-  e = launch_zstd_pass(items + h, status + h, n_items - h, dst + (uint64_t)h * slot_bytes, slot_bytes, B, Z.s2,
-                       nullptr);
-  if (e != hipSuccess) return e;
-  if ((e = hipEventRecord(Z.ev_done, Z.s2)) != hipSuccess) return e;
-  return hipStreamWaitEvent(s, Z.ev_done, 0);
 }
 
 }  // namespace zgpu

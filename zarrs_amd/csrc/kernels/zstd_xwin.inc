@@ -29,18 +29,13 @@
 // EXT | item position); k_zstd_ext_round then resolves the external references by pointer jumping
 // over the whole output (ping-pong arrays, one launch per round: every hop of a chain leaves a window
 // for an earlier one, so ceil(log2(an item's windows)) + 1 rounds; the bound on the windows is at the
-// zstd_ext_rounds in zstd.hip), and k_zstd_par_finish checks that no reference is left and the frame
+// rounds rule in zstd_launch.cpp), and k_zstd_par_finish checks that no reference is left and the frame
 // checksums.
 // Reference behaviour: zarrs/src/array/codec/bytes_to_bytes/zstd/zstd_codec.rs:113-130 (libzstd
 // ZSTD_decompress; RFC 8878 3.1.1.4 sequence execution).
 namespace xwin {
-#ifndef ZG_XWIN_THREADS
-#define ZG_XWIN_THREADS 1024
-#endif
-constexpr uint32_t THREADS = ZG_XWIN_THREADS, NWAVE = THREADS / 64;
-constexpr uint32_t CELLS = 32768;         // cells per window (u16: bit 15 resolved, else a 15-bit index)
-constexpr uint32_t W = CELLS - 16;        // window span from its 16-B aligned base
-constexpr uint32_t T = THREADS == 512 ? 768 : 1024;  // sequence table entries per load
+// (THREADS, CELLS, W, T and WSPAN: zstd_params.hpp)
+constexpr uint32_t NWAVE = THREADS / 64;
 constexpr uint32_t E = (T + THREADS - 1) / THREADS;  // table entries per thread
 constexpr uint32_t PER_LANE = CELLS / THREADS;  // cells per lane: one per row of its wave (64 or 32)
 constexpr uint32_t ROWS = CELLS / 64;           // rows of 64 cells (a wave's row: one cell per lane)
@@ -64,7 +59,6 @@ struct Cell<true> {
   static constexpr uint32_t RES = 0x80000000u, EXT = 0x40000000u, DONE = 0xC0000000u;
 };
 constexpr uint32_t EXT_NONE = 0xFFFFFFFFu;       // ext array: resolved
-constexpr uint32_t WSPAN = W - 16;               // latency mode: bytes of a block per workgroup
 constexpr uint32_t WPB = (BLOCK_MAX + WSPAN - 1) / WSPAN;  // latency mode: workgroups per block
 
 template <bool PAR>
@@ -525,9 +519,9 @@ __global__ __launch_bounds__(256) void k_zstd_ext_round(const uint32_t *ea, uint
 // Latency mode, last step: frame checksums over the resolved output and the items' decoded records
 // (one wave per item). ext_fin / cnt_last: the ext array and the reference count the last round left;
 // an item with a reference still in it (only when the count is not 0) is an error, never status 0
-// over unresolved bytes. With zstd_ext_rounds' bound no legal frame leaves a reference, so no test
-// reaches that branch: it is a guard for a bound that a later change breaks. lat_count (nullable): the
-// items finished here.
+// over unresolved bytes. With the round count's bound (zstd_launch.cpp) no legal frame leaves a
+// reference, so no test reaches that branch: it is a guard for a bound that a later change breaks.
+// lat_count (nullable): the items finished here.
 __global__ __launch_bounds__(64) void k_zstd_par_finish(ZgItem *items, uint32_t *status, const ZBlk *blks,
                                                         uint32_t blk_cap, const uint32_t *nblk,
                                                         const uint32_t *zmode, uint8_t *dst, uint64_t slot_bytes,

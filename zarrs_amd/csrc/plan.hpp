@@ -104,40 +104,22 @@ struct zgpu_plan {
 
   struct {
     ZstdScratch zs{};  // block-parallel zstd scratch (allocated when the chain has zstd)
-    // side stream of the zstd sequence decoder (ZGPU_ZSTD_FORK=0 keeps one stream), and the second
-    // half's stream (zstd_split)
-    SideLane side, split;
+    SideLane side;     // side stream of the zstd sequence decoder (ZGPU_ONE_STREAM keeps one stream)
     // serial fallback: skipped once an execution of this plan had no serial item (a later one that
     // has some is re-run by plan_statuses with the fallback launched)
     bool serial_off = false, serial_skipped = false;
-    uint32_t *d_zser = nullptr;
   } zstd;
   void zstd_fork(ZstdScratch &Z, hipStream_t s) {
-    static const bool on = [] {
-      const char *e = std::getenv("ZGPU_ZSTD_FORK");
-      return !e || std::atoi(e) != 0;
-    }();
-    if (!on || (flags & ZGPU_ONE_STREAM)) return;
+    if (flags & ZGPU_ONE_STREAM) return;
     zstd.side.ensure(s);
     Z.side = zstd.side.stream;
     Z.ev_fork = zstd.side.ev[0];
     Z.ev_join = zstd.side.ev[1];
   }
-  // zstd in two pipelined halves (ZstdScratch::s2; blosc stream tables of many frames): opt-in with
-  // ZGPU_ZSTD_SPLIT=1 (blosc-zstd bench 32.6 -> 35.6 ms with it: the halves' kernels contend more than
-  // they overlap, profiles/r04an_zstd_split_ab.txt)
-  void zstd_split(ZstdScratch &Z, hipStream_t s) {
-    const char *e = std::getenv("ZGPU_ZSTD_SPLIT");  // read per call (tests switch it)
-    if (!e || std::atoi(e) == 0 || !Z.side) return;
-    zstd.split.ensure(s);
-    Z.s2 = zstd.split.stream;
-    Z.ev_half = zstd.split.ev[0];
-    Z.ev_done = zstd.split.ev[1];
-  }
   // blosc stage scratch (the stream table is sized from the frame headers)
   struct {
-    Grow info, bases, subs, sub_status, sub_kind, blocks, tmp, zblks, znblk, zmode, zlit, zseq, zaux, zser, lzl, zseg,
-        zrec, zalias, znorm;
+    Grow info, bases, subs, sub_status, sub_kind, blocks, tmp, zaux, lzl, zseg;
+    Grow zs[ZSTD_SCRATCH_BUFFERS];  // the zstd streams' scratch (zstd_bind)
     BlCaps caps{};  // stream-table capacities recorded by the first execution
     bool caps_valid = false, caps_seen = false;
     uint8_t *h = nullptr;        // pinned: BlInfo read-back (first execution)
@@ -169,7 +151,6 @@ struct zgpu_plan {
     }
     if (own.order_ev) (void)hipEventDestroy(own.order_ev);
     zstd.side.destroy();
-    zstd.split.destroy();
     mem.release();
   }
 };

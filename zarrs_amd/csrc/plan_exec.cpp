@@ -20,6 +20,26 @@
 
 using namespace zgpu;
 
+// Sizes the zstd scratch of n items of slot_bytes (zstd_scratch_sizes) and binds it to Z: alloc(k, bytes)
+// gives buffer k of ZSTD_SCRATCH_BUFFERS (bytes > 0). A buffer the sizes leave out stays null.
+template <class Alloc>
+static void zstd_bind(ZstdScratch &Z, uint64_t n, uint64_t slot_bytes, const ZstdWants &wants, Alloc alloc) {
+  const ZstdScratchSizes S = zstd_scratch_sizes(n, slot_bytes, device_cu_count(), wants);
+  auto get = [&](int k, auto *&p, uint64_t bytes) { p = bytes ? (decltype(+p))alloc(k, bytes) : nullptr; };
+  Z.blk_cap = S.blk_cap, Z.lit_stride = S.lit_stride, Z.seq_cap = S.seq_cap, Z.lit_rec_wgs = S.lit_rec_wgs;
+  get(0, Z.blks, S.blks);
+  get(1, Z.norm, S.norm);
+  get(2, Z.nblk, S.nblk);
+  get(3, Z.mode, S.mode);
+  get(4, Z.lit, S.lit);
+  get(5, Z.seq, S.seq);
+  get(6, Z.ser_list, S.ser_list);
+  get(7, Z.lit_rec, S.lit_rec);
+  get(8, Z.alias, S.alias);
+  get(9, Z.ext, S.ext);
+  get(ZSTD_SCRATCH_BUFFERS - 1, Z.ext_cnt, S.ext_cnt);
+}
+
 void plan_upload(zgpu_plan &P, hipStream_t us) {
   const size_t ni = P.L.items.size();
   if (ni) {
@@ -52,28 +72,9 @@ void plan_upload(zgpu_plan &P, hipStream_t us) {
         P.bz2.bz.base = P.mem.dev<uint8_t>(items_bytes + bz2_list_bytes(P.bz2.bz.round_items, P.bz2.bz.cap));
         P.bz2.bz.lists = (uint32_t *)(P.bz2.bz.base + items_bytes);
       }
-      if (s.kind == ST_ZSTD && !P.zstd.zs.blks) {
-        uint64_t blk_bytes;
-        zstd_scratch_layout(P.L.slot_bytes, P.zstd.zs.blk_cap, blk_bytes, P.zstd.zs.lit_stride, P.zstd.zs.seq_cap);
-        P.zstd.zs.blks = P.mem.dev<uint8_t>(ni * (uint64_t)P.zstd.zs.blk_cap * blk_bytes);
-        P.zstd.zs.norm = (int16_t *)P.mem.dev<uint8_t>(ni * (uint64_t)P.zstd.zs.blk_cap * zstd_norm_bytes());
-        P.zstd.zs.nblk = P.mem.dev<uint32_t>(ni);
-        P.zstd.zs.mode = P.mem.dev<uint32_t>(ni);
-        P.zstd.zs.lit = P.mem.dev<uint8_t>(ni * P.zstd.zs.lit_stride);
-        P.zstd.zs.seq = P.mem.dev<uint32_t>(ni * P.zstd.zs.seq_cap * 3);
-        P.zstd.d_zser = P.mem.dev<uint32_t>(ni);
-        P.zstd.zs.ser_list = P.zstd.d_zser;
-        if (const uint64_t rb = zstd_lit_rec_bytes(P.zstd.zs.lit_rec_wgs)) P.zstd.zs.lit_rec = P.mem.dev<uint8_t>(rb);
-        static const uint64_t par_max = [] {  // ZGPU_ZSTD_XPAR_MB: the latency mode's batch limit (tuning)
-          const char *e = std::getenv("ZGPU_ZSTD_XPAR_MB");
-          return e ? (uint64_t)std::strtoull(e, nullptr, 10) << 20 : ZPAR_MAX_BYTES;
-        }();
-        if (ni * P.L.slot_bytes <= par_max) {  // the window executor's latency mode (few frames)
-          P.zstd.zs.ext = P.mem.dev<uint32_t>(2 * ni * P.L.slot_bytes);
-          P.zstd.zs.ext_cnt = P.mem.dev<unsigned long long>(ZEXT_ROUNDS);
-          P.zstd.zs.ext_items = ni;
-        }
-      }
+      if (s.kind == ST_ZSTD && !P.zstd.zs.blks)  // (the latency mode: a plan's own stage, few frames)
+        zstd_bind(P.zstd.zs, ni, P.L.slot_bytes, ZstdWants{false, true, zstd_knobs_from_env()},
+                  [&](int, uint64_t bytes) { return P.mem.dev<uint8_t>(bytes); });
     }
   }
   // the longest encoded item: known for plain chunks; an inner chunk's length comes from its shard's
@@ -105,7 +106,6 @@ void plan_upload(zgpu_plan &P, hipStream_t us) {
   P.zstd.zs.lat_count = P.d_counter + CTR_ZSTD_LATENCY;
   P.zstd.zs.ser_count = P.d_counter + CTR_ZSTD_NSER;
   P.zstd.zs.max_nblk = P.d_counter + CTR_ZSTD_MAXBLK;
-  if (const char *e = std::getenv("ZGPU_ZSTD_FORCE_SERIAL")) P.zstd.zs.force_serial = std::atoi(e) != 0;
   if (!P.L.shards.empty()) {
     P.d_shards = P.mem.dev<ZgShard>(P.L.shards.size());
     P.d_index = P.mem.dev<uint64_t>(P.L.shards.size() * P.L.ispec.n_inner * 2);
@@ -198,27 +198,16 @@ static void blosc_stage(zgpu_plan &P, const Stage &st, uint8_t *out, hipStream_t
   }
   D.lz_list = (D.n_lz4 || D.n_blosclz || D.n_snappy) ? (uint32_t *)P.grow(P.blosc.lzl, 2 * (D.n_sub + 1) * 4) : nullptr;
   if (D.n_zstd) {
-    uint64_t blk_bytes;
-    zstd_scratch_layout(D.sub_slot, D.zs.blk_cap, blk_bytes, D.zs.lit_stride, D.zs.seq_cap);
-    D.zs.blks = P.grow(P.blosc.zblks, D.n_sub * (uint64_t)D.zs.blk_cap * blk_bytes);
-    D.zs.norm = (int16_t *)P.grow(P.blosc.znorm, D.n_sub * (uint64_t)D.zs.blk_cap * zstd_norm_bytes());
-    D.zs.nblk = (uint32_t *)P.grow(P.blosc.znblk, D.n_sub * 4);
-    D.zs.mode = (uint32_t *)P.grow(P.blosc.zmode, D.n_sub * 4);
-    D.zs.lit = (uint8_t *)P.grow(P.blosc.zlit, D.n_sub * D.zs.lit_stride);
-    D.zs.seq = (uint32_t *)P.grow(P.blosc.zseq, D.n_sub * D.zs.seq_cap * 12);
-    D.zs.counters = P.zstd.zs.counters;
-    D.zs.max_nblk = P.zstd.zs.max_nblk;
-    D.zs.force_serial = P.zstd.zs.force_serial;
-    D.zs.ser_list = (uint32_t *)P.grow(P.blosc.zser, D.n_sub * 4);
-    if (const uint64_t rb = zstd_lit_rec_bytes(D.zs.lit_rec_wgs)) D.zs.lit_rec = (uint8_t *)P.grow(P.blosc.zrec, rb);
     // k_blosc_finish reads raw / rle / literal-only zstd blocks where they lie (ZGPU_BLOSC_ALIAS=0: off)
     const char *ae = std::getenv("ZGPU_BLOSC_ALIAS");  // read per call (tests switch it)
-    const bool alias_on = !ae || std::atoi(ae) != 0;
-    D.zs.alias = alias_on ? (uint64_t *)P.grow(P.blosc.zalias, D.n_sub * 3 * ZALIAS * 8) : nullptr;
+    D.zs.knobs = zstd_knobs_from_env();
+    zstd_bind(D.zs, D.n_sub, D.sub_slot, ZstdWants{!ae || std::atoi(ae) != 0, false, D.zs.knobs},
+              [&](int k, uint64_t bytes) { return P.grow(P.blosc.zs[k], bytes); });
+    D.zs.counters = P.zstd.zs.counters;
+    D.zs.max_nblk = P.zstd.zs.max_nblk;
     D.zs.ser_count = P.zstd.zs.ser_count;
     D.zs.launch_serial = P.zstd.zs.launch_serial;
     P.zstd_fork(D.zs, s);
-    P.zstd_split(D.zs, s);
   }
   // the layout (bases, inert tails past this execution's totals) is always computed on the device
   HIPCHK(launch_blosc_layout(info, ni, d_bases, caps, D, s));
@@ -320,6 +309,7 @@ void plan_enqueue(zgpu_plan &P, uint8_t *out, hipStream_t s) {
         break;
       case ST_ZSTD:
         P.zstd_fork(P.zstd.zs, s);
+        P.zstd.zs.knobs = zstd_knobs_from_env();
         P.zstd.zs.lits_first = (P.flags & ZGPU_ZSTD_LITS_FIRST) && !P.zstd.zs.side ? 1u : 0u;
         HIPCHK(launch_zstd(P.d_items, P.d_status, ni, P.d_pool[st.pool], P.L.slot_bytes, P.zstd.zs, s));
         break;
