@@ -20,6 +20,11 @@
  *                       <- Array::retrieve_array_subset_into (zarrs/src/array/array_ops/
  *                          array_read_ops_common.rs:20-179, array_read_ops_array.rs:231-375):
  *                          the array-level batched driver that feeds zgpu_decode_batch.
+ *   zgpu_retrieve_elements / zgpu_points_chunks
+ *                       <- Indexer for &[ArrayIndices] / Vec<ArrayIndices> (zarrs_chunk_grid/src/indexer.rs:
+ *                          285-392) read through ArrayPartialDecoderTraits::partial_decode(&dyn Indexer),
+ *                          which partial_decode_fixed_indexer serves (sharding/
+ *                          sharding_partial_decoder_sync.rs:492-560): elements by a list of coordinates.
  *   zgpu_decode_files / zgpu_retrieve_array_subset_files
  *                       <- the same, with the encoded chunks read from a filesystem store:
  *                          FilesystemStore::get / get_partial_many (zarrs_filesystem/src/lib.rs:
@@ -370,7 +375,11 @@ void zgpu_group_destroy(zgpu_group *group);
 #define ZGPU_CTR_STORE_ENCODED 10 /* zgpu_store_array_subset: leaf chunks encoded                          */
 #define ZGPU_CTR_STORE_CARRIED 11 /* zgpu_store_array_subset: untouched inner chunks whose encoded bytes were
                                     copied from the old shard into the new one                           */
-#define ZGPU_N_COUNTERS 12
+#define ZGPU_CTR_POINT_LEAVES 12 /* zgpu_retrieve_elements: distinct leaves (chunks, or inner chunks of shards) the
+                                    points touch: staged, read from the cache, or read as the fill value    */
+#define ZGPU_CTR_POINT_ROUNDS 13 /* zgpu_retrieve_elements: decode + gather rounds: 1 when the touched leaves fit
+                                    ZGPU_POINTS_SCRATCH_MB (and for the cache), more when they are cut     */
+#define ZGPU_N_COUNTERS 14
 uint32_t zgpu_plan_counters(const zgpu_plan *plan, uint64_t *out, uint32_t n);
 uint32_t zgpu_last_counters(uint64_t *out, uint32_t n);
 
@@ -392,6 +401,62 @@ int zgpu_retrieve_array_subset(zgpu_chain *chain, uint32_t ndim, const uint64_t 
                                const uint64_t *chunk_lens, const uint64_t *sel_start,
                                const uint64_t *sel_shape, void *out, uint32_t flags,
                                void *hip_stream);
+
+/*
+ * Read by coordinates: Indexer for &[ArrayIndices] / Vec<ArrayIndices> (zarrs_chunk_grid/src/indexer.rs:
+ * 285-392), served as partial_decode_fixed_indexer serves it (sharding/sharding_partial_decoder_sync.rs:
+ * 492-560): every touched leaf is decoded once and the elements are picked out of it -- here in HBM.
+ *
+ * zgpu_points_chunks: the distinct C-order linear chunk-grid indices that the n points touch, ascending,
+ * for a caller to look up only those keys in its store. Pure host code (no context, no device).
+ * indices: [n][ndim] u64, row-major. *n_chunks receives their number; entries are written only while
+ * they fit cap (call with cap 0 to size the array, as zgpu_store_classify). A coordinate >=
+ * array_shape[d] (IndexerError::OutOfBounds): ZGPU_INVALID_ARGUMENT, and zgpu_last_error names the first
+ * such point and its axis. n == 0: ZGPU_OK and no chunks.
+ */
+int zgpu_points_chunks(uint32_t ndim, const uint64_t *array_shape, const uint64_t *chunk_shape,
+                       const uint64_t *indices, uint64_t n, uint64_t *chunks, uint64_t cap, uint64_t *n_chunks);
+/*
+ * The leaf grid zgpu_retrieve_elements works on, without a device: *n_leaves (optional) receives the
+ * number of leaves of the array (chunk grid x leaves per chunk; leaf_shape NULL: the chunk is the leaf),
+ * which the call holds against ZGPU_POINTS_BITMAP_MAX_BYTES * 8, and *wide (optional) whether its kernels
+ * index with 64-bit arithmetic: 1 when an extent of the array or of the leaf, or the number of leaves,
+ * does not fit 32 bits. ZGPU_INVALID_ARGUMENT for a zero extent, a chunk that is no multiple of the leaf,
+ * or a grid of 2^64 leaves or more.
+ */
+int zgpu_points_geometry(uint32_t ndim, const uint64_t *array_shape, const uint64_t *chunk_shape,
+                         const uint64_t *leaf_shape, uint64_t *n_leaves, uint32_t *wide);
+/*
+ * zgpu_retrieve_elements: out[i] = the element at indices[i] (out holds n elements: Indexer::output_shape
+ * is [n]); duplicate points each get their element. chunk_ptrs / chunk_lens as for
+ * zgpu_retrieve_array_subset (NULL: the key is missing, its points read the fill value); only the chunks
+ * the points touch are read. flags: ZGPU_ENC_DEVICE, ZGPU_OUT_DEVICE and ZGPU_NO_VALIDATE as for decoding;
+ * ZGPU_IDX_DEVICE: indices is device memory (host indices are uploaded; one path for both). Synchronous
+ * with respect to the host, like zgpu_decode_batch. Every chain zgpu_decode_batch accepts works here.
+ * The decode granule is the LEAF: the chunk, or, for a chain whose array->bytes codec is sharding_indexed,
+ * the outermost sharding's inner chunk (carried back through the transposes in front of it into the
+ * chunk's frame; value codecs in front of it change nothing about the rule). Each touched leaf whose key
+ * is present is decoded once (ZGPU_CTR_ITEMS), in one batch per round, into staging bounded by
+ * ZGPU_POINTS_SCRATCH_MB (environment, read per call; default 1024, a policy choice): more leaves than fit
+ * take more rounds, at least one leaf each (ZGPU_CTR_POINT_ROUNDS). Checksums follow the descriptor rule of
+ * zgpu_decode_batch: a whole unsharded chunk takes the full decode path and is verified; an inner chunk
+ * of a shard takes the partial-decoder path: its crc32c is stripped, not verified, and the shard index
+ * is verified.
+ * Errors: a point out of bounds fails the whole call with ZGPU_INVALID_ARGUMENT before anything is decoded
+ * or written (zgpu_last_error names the first such point); a kernel finds it, for host indices too. A
+ * touched leaf that fails to decode gives the call that leaf's status, the first in ascending (chunk,
+ * leaf) order; there is no per-point status: the elements taken from failed leaves are unspecified, all
+ * others are complete. A corrupt leaf that no point touches does not matter. The touched leaves are found
+ * through a dense bitmap of one bit per leaf of the array, limited to ZGPU_POINTS_BITMAP_MAX_BYTES
+ * (16 MiB: 2^27 leaves); an array of more leaves returns ZGPU_UNSUPPORTED (no sparse fallback).
+ * Element sizes 1, 2, 4, 8 and 16; a device out is aligned to min(element size, 8), indices to 8.
+ */
+#define ZGPU_IDX_DEVICE 0x100u
+#define ZGPU_POINTS_BITMAP_MAX_BYTES (16u << 20)
+int zgpu_retrieve_elements(zgpu_chain *chain, uint32_t ndim, const uint64_t *array_shape,
+                           const uint64_t *chunk_shape, const void *const *chunk_ptrs,
+                           const uint64_t *chunk_lens, const void *indices, uint64_t n,
+                           void *out, uint32_t flags, void *hip_stream);
 
 /*
  * zgpu_retrieve_array_subset over several GPUs of one node from one process (one chain per device,
@@ -585,6 +650,18 @@ int zgpu_cache_retrieve_array_subset(zgpu_cache *cache, zgpu_chain *chain, uint3
                                      const uint64_t *chunk_shape, const void *const *chunk_ptrs,
                                      const uint64_t *chunk_lens, const uint64_t *sel_start, const uint64_t *sel_shape,
                                      void *out, uint32_t flags, void *hip_stream);
+
+/*
+ * zgpu_retrieve_elements through the cache (ArrayCached with an Indexer of coordinates). The granule is the
+ * chunk, which is what the cache holds: the touched chunks that miss are decoded whole into their slots in
+ * one batch (verified, as a subset read), the elements are then gathered straight from the pool (no
+ * staging, one round). Hits and misses count each touched chunk once. A read touching more chunks than
+ * the cache holds takes zgpu_retrieve_elements' path and caches nothing new.
+ */
+int zgpu_cache_retrieve_elements(zgpu_cache *cache, zgpu_chain *chain, uint32_t ndim, const uint64_t *array_shape,
+                                 const uint64_t *chunk_shape, const void *const *chunk_ptrs,
+                                 const uint64_t *chunk_lens, const void *indices, uint64_t n, void *out,
+                                 uint32_t flags, void *hip_stream);
 
 /*
  * DLPack export of a decoded subset left in HBM (the reference exports CPU tensors only:

@@ -30,6 +30,12 @@ pub const ZGPU_ONE_STREAM: u32 = 0x10;
 pub const ZGPU_ZSTD_LITS_FIRST: u32 = 0x40;
 /// Concurrent host-in/host-out calls on one chain share one GPU batch (zgpu.h ZGPU_COALESCE).
 pub const ZGPU_COALESCE: u32 = 0x20;
+/// zgpu_store_array_subset: store chunks that equal the fill value everywhere (not bound here yet).
+pub const ZGPU_STORE_EMPTY_CHUNKS: u32 = 0x80;
+/// zgpu_retrieve_elements: `indices` is device memory.
+pub const ZGPU_IDX_DEVICE: u32 = 0x100;
+/// zgpu_retrieve_elements: the dense bitmap of one bit per leaf of the array may not pass this size.
+pub const ZGPU_POINTS_BITMAP_MAX_BYTES: u64 = 16 << 20;
 
 #[repr(C)]
 pub struct zgpu_ctx {
@@ -45,6 +51,12 @@ pub struct zgpu_chain {
 pub struct zgpu_result {
     _opaque: [u8; 0],
 }
+/// An HBM-resident decoded-chunk cache (`zgpu_cache_create`, not bound here yet; zgpu_cache_retrieve_elements
+/// takes one).
+#[repr(C)]
+pub struct zgpu_cache {
+    _opaque: [u8; 0],
+}
 /// A plan group (`zgpu_group_create`): the independent parts of one batch decoded by one call.
 #[repr(C)]
 pub struct zgpu_group {
@@ -57,7 +69,13 @@ pub const ZGPU_CTR_ITEMS: usize = 5;
 pub const ZGPU_CTR_ZSTD_LATENCY: usize = 6;
 pub const ZGPU_CTR_BZ2_BLOCKS: usize = 7;
 pub const ZGPU_CTR_BZ2_ROUNDS: usize = 8;
-pub const ZGPU_N_COUNTERS: usize = 9;
+pub const ZGPU_CTR_STORE_DECODED: usize = 9;
+pub const ZGPU_CTR_STORE_ENCODED: usize = 10;
+pub const ZGPU_CTR_STORE_CARRIED: usize = 11;
+/// zgpu_retrieve_elements: distinct leaves the points touch; decode + gather rounds.
+pub const ZGPU_CTR_POINT_LEAVES: usize = 12;
+pub const ZGPU_CTR_POINT_ROUNDS: usize = 13;
+pub const ZGPU_N_COUNTERS: usize = 14;
 
 /// zgpu_encode_desc: one chunk of a device-resident array encoded into `dst`.
 #[repr(C)]
@@ -206,5 +224,55 @@ unsafe extern "C" {
         sel_shape: *const u64,
         out: *mut c_void,
         flags: u32,
+    ) -> c_int;
+    /// Indexer for &[ArrayIndices] (zarrs_chunk_grid/src/indexer.rs:285-392): the distinct chunks the points
+    /// touch, ascending; pure host code. Two-call sizing: cap 0 sizes `chunks`.
+    pub fn zgpu_points_chunks(
+        ndim: u32,
+        array_shape: *const u64,
+        chunk_shape: *const u64,
+        indices: *const u64,
+        n: u64,
+        chunks: *mut u64,
+        cap: u64,
+        n_chunks: *mut u64,
+    ) -> c_int;
+    /// The leaf grid of zgpu_retrieve_elements: its number of leaves and whether the kernels index in 64 bits.
+    pub fn zgpu_points_geometry(
+        ndim: u32,
+        array_shape: *const u64,
+        chunk_shape: *const u64,
+        leaf_shape: *const u64,
+        n_leaves: *mut u64,
+        wide: *mut u32,
+    ) -> c_int;
+    /// partial_decode_fixed_indexer (sharding/sharding_partial_decoder_sync.rs:492-560) on the GPU:
+    /// out[i] = the element at indices[i] ([n][ndim] u64; device memory with ZGPU_IDX_DEVICE).
+    pub fn zgpu_retrieve_elements(
+        chain: *mut zgpu_chain,
+        ndim: u32,
+        array_shape: *const u64,
+        chunk_shape: *const u64,
+        chunk_ptrs: *const *const c_void,
+        chunk_lens: *const u64,
+        indices: *const c_void,
+        n: u64,
+        out: *mut c_void,
+        flags: u32,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    pub fn zgpu_cache_retrieve_elements(
+        cache: *mut zgpu_cache,
+        chain: *mut zgpu_chain,
+        ndim: u32,
+        array_shape: *const u64,
+        chunk_shape: *const u64,
+        chunk_ptrs: *const *const c_void,
+        chunk_lens: *const u64,
+        indices: *const c_void,
+        n: u64,
+        out: *mut c_void,
+        flags: u32,
+        hip_stream: *mut c_void,
     ) -> c_int;
 }

@@ -46,12 +46,15 @@ EXPORTS = [
     "zgpu_group_create", "zgpu_group_execute", "zgpu_group_status", "zgpu_group_layout",
     "zgpu_group_algorithmic_bytes", "zgpu_group_counters", "zgpu_group_destroy", "zgpu_plan_scatter_path",
     "zgpu_store_array_subset", "zgpu_store_entry_copy", "zgpu_store_classify",
+    "zgpu_points_chunks", "zgpu_points_geometry", "zgpu_retrieve_elements", "zgpu_cache_retrieve_elements",
 ]
 SCATTER_ROWS, SCATTER_TILED, SCATTER_GENERIC, SCATTER_TILED_PERSISTENT = range(4)  # zgpu_plan_scatter_path
 CTR_ENC_BYTES, CTR_ZSTD_SERIAL, CTR_ZSTD_PARALLEL, CTR_BLOSC_RERUN, CTR_BLOSC_BLOCKS, CTR_ITEMS, \
     CTR_ZSTD_LATENCY, CTR_BZ2_BLOCKS, CTR_BZ2_ROUNDS, CTR_STORE_DECODED, CTR_STORE_ENCODED, \
-    CTR_STORE_CARRIED = range(12)
-N_COUNTERS = 12
+    CTR_STORE_CARRIED, CTR_POINT_LEAVES, CTR_POINT_ROUNDS = range(14)
+N_COUNTERS = 14
+IDX_DEVICE = 0x100  # zgpu_retrieve_elements flag: the indices are device memory
+POINTS_BITMAP_MAX_BYTES = 16 << 20  # zgpu_retrieve_elements: one bit per leaf of the array
 STORE_EMPTY_CHUNKS = 0x80  # zgpu_store_array_subset flag
 STORE_SET, STORE_ERASE = 1, 2  # zgpu_store_entry.action
 LEAF_UNTOUCHED, LEAF_PARTIAL, LEAF_COVERED = range(3)  # zgpu_store_classify
@@ -212,6 +215,10 @@ def load() -> C.CDLL:
                                           C.POINTER(C.POINTER(StoreEntry)), P64, C.POINTER(vp), vp]
     L.zgpu_store_entry_copy.argtypes = [vp, C.POINTER(StoreEntry), vp, vp]
     L.zgpu_store_classify.argtypes = [u32, P64, P64, P64, P64, P64, P64, C.POINTER(C.c_uint8), u64, P64]
+    L.zgpu_points_chunks.argtypes = [u32, P64, P64, vp, u64, P64, u64, P64]
+    L.zgpu_points_geometry.argtypes = [u32, P64, P64, P64, P64, C.POINTER(u32)]
+    L.zgpu_retrieve_elements.argtypes = [vp, u32, P64, P64, C.POINTER(vp), P64, vp, u64, vp, u32, vp]
+    L.zgpu_cache_retrieve_elements.argtypes = [vp, vp, u32, P64, P64, C.POINTER(vp), P64, vp, u64, vp, u32, vp]
     _lib = L
     return L
 
@@ -226,7 +233,22 @@ def last_counters() -> dict:
     load().zgpu_last_counters(buf, N_COUNTERS)
     return {"enc_bytes": buf[0], "zstd_serial": buf[1], "zstd_parallel": buf[2], "blosc_rerun": buf[3],
             "blosc_blocks": buf[4], "zstd_latency": buf[6], "bz2_blocks": buf[7], "bz2_rounds": buf[8],
-            "store_decoded": buf[9], "store_encoded": buf[10], "store_carried": buf[11]}
+            "store_decoded": buf[9], "store_encoded": buf[10], "store_carried": buf[11],
+            "point_leaves": buf[12], "point_rounds": buf[13]}
+
+
+def points_chunks(array_shape, chunk_shape, indices) -> list:
+    """zgpu_points_chunks: the distinct C-order linear chunk-grid indices the points touch, ascending
+    (no device involved). indices: an (n, ndim) array of non-negative integers."""
+    import numpy as np
+    nd = len(array_shape)
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1, nd)
+    args = (nd, u64s(array_shape), u64s(chunk_shape), idx.ctypes.data, idx.shape[0])
+    n = C.c_uint64()
+    check(load().zgpu_points_chunks(*args, None, 0, C.byref(n)))
+    chunks = (C.c_uint64 * max(n.value, 1))()
+    check(load().zgpu_points_chunks(*args, chunks, n.value, C.byref(n)))
+    return list(chunks[:n.value])
 
 
 def store_classify(array_shape, chunk_shape, leaf_shape, start, shape):
@@ -244,6 +266,14 @@ def store_classify(array_shape, chunk_shape, leaf_shape, start, shape):
     cls = (C.c_uint8 * max(n.value * lpc, 1))()
     check(load().zgpu_store_classify(*args, chunks, cls, n.value, C.byref(n)))
     return [(int(chunks[k]), list(cls[k * lpc:(k + 1) * lpc])) for k in range(n.value)]
+
+
+def points_geometry(array_shape, chunk_shape, leaf_shape=None):
+    """zgpu_points_geometry: (leaves of the array, whether zgpu_retrieve_elements indexes in 64 bits)."""
+    n, wide = C.c_uint64(), C.c_uint32()
+    check(load().zgpu_points_geometry(len(array_shape), u64s(array_shape), u64s(chunk_shape),
+                                      u64s(leaf_shape) if leaf_shape is not None else None, C.byref(n), C.byref(wide)))
+    return n.value, bool(wide.value)
 
 
 def last_size_mismatch():

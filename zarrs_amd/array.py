@@ -187,25 +187,113 @@ class Array:
             if skip_covered and all(int(st) <= i * c and (i + 1) * c <= int(st) + int(sh)
                                     for i, c, st, sh in zip(idx, self.chunk_shape, start, shape)):
                 continue
-            v = self.store.get(self.chunk_key(idx))
-            if v is None:
-                continue
-            lin = int(np.ravel_multi_index(idx, grid))
-            if self.store.device:
-                ptrs[lin] = v.data_ptr() if v.numel() else None
-                lens[lin] = v.numel()
-                keep.append(v)
-                if not v.numel():  # an empty object is still present: give it a valid address
-                    import torch
-                    t = torch.empty(1, dtype=torch.uint8, device=v.device)
-                    keep.append(t)
-                    ptrs[lin] = t.data_ptr()
-            else:
-                b = np.frombuffer(v, dtype=np.uint8) if len(v) else np.zeros(1, np.uint8)
-                keep.append(b)
-                ptrs[lin] = b.ctypes.data
-                lens[lin] = len(v)
+            self._lookup(idx, int(np.ravel_multi_index(idx, grid)), ptrs, lens, keep)
         return ptrs, lens, keep
+
+    def _lookup(self, idx, lin, ptrs, lens, keep) -> None:
+        """The chunk at grid index idx (linear index lin) into the pointer tables, if its key exists."""
+        v = self.store.get(self.chunk_key(idx))
+        if v is None:
+            return
+        if self.store.device:
+            ptrs[lin] = v.data_ptr() if v.numel() else None
+            lens[lin] = v.numel()
+            keep.append(v)
+            if not v.numel():  # an empty object is still present: give it a valid address
+                import torch
+                t = torch.empty(1, dtype=torch.uint8, device=v.device)
+                keep.append(t)
+                ptrs[lin] = t.data_ptr()
+        else:
+            b = np.frombuffer(v, dtype=np.uint8) if len(v) else np.zeros(1, np.uint8)
+            keep.append(b)
+            ptrs[lin] = b.ctypes.data
+            lens[lin] = len(v)
+
+    def _point_tables(self, indices):
+        """(pointer to the indices, n, on the device, pointer tables, what to keep alive) of a read by
+        coordinates. indices: an (n, ndim) integer array (numpy, or a torch tensor; a list of points is
+        read as such an array) or a tuple of ndim 1-D arrays. Device indices over a DeviceStore stay on the device, and every chunk's pointer goes
+        into the tables; otherwise the indices go through the host, where zgpu_points_chunks selects
+        the keys to fetch."""
+        nd = self.ndim
+        try:
+            import torch
+        except ImportError:  # pragma: no cover
+            torch = None
+        is_t = lambda v: torch is not None and isinstance(v, torch.Tensor)  # noqa: E731
+        if isinstance(indices, tuple):  # (a list is a list of points, as numpy reads it)
+            if len(indices) != nd or not all(hasattr(v, "shape") for v in indices):
+                raise L.ZgpuError(L.INVALID_ARGUMENT, f"retrieve_elements: {len(indices)} index arrays, rank {nd}")
+            if all(is_t(v) and v.is_cuda for v in indices):
+                indices = torch.stack([v.reshape(-1) for v in indices], dim=1)
+            else:
+                indices = np.stack([np.asarray(v.cpu() if is_t(v) else v).reshape(-1) for v in indices], axis=1)
+        if is_t(indices) and indices.is_cuda and self.store.device:
+            if indices.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
+                if indices.dtype.is_floating_point or indices.dtype == torch.bool:
+                    raise L.ZgpuError(L.INVALID_ARGUMENT, "retrieve_elements: indices must be integers")
+                indices = indices.to(torch.int64)
+            if indices.dim() != 2 or indices.shape[1] != nd:
+                raise L.ZgpuError(L.INVALID_ARGUMENT, f"retrieve_elements: indices of shape {list(indices.shape)}")
+            # (a negative int64 is a coordinate >= 2^63 to the bounds check: rejected there, no wrap-around)
+            indices = indices.contiguous()
+            ptrs, lens, keep = self._tables([0] * nd, self.shape)
+            return indices.data_ptr(), int(indices.shape[0]), True, ptrs, lens, keep + [indices]
+        if is_t(indices):
+            indices = indices.cpu().numpy()
+        indices = np.asarray(indices)
+        if indices.size == 0:
+            indices = indices.reshape(0, nd).astype(np.uint64)
+        if indices.dtype.kind not in "iu":
+            raise L.ZgpuError(L.INVALID_ARGUMENT, "retrieve_elements: indices must be integers")
+        if indices.ndim != 2 or indices.shape[1] != nd:
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"retrieve_elements: indices of shape {list(indices.shape)}")
+        if indices.dtype.kind == "i" and indices.size and int(indices.min()) < 0:
+            raise L.ZgpuError(L.INVALID_ARGUMENT, "retrieve_elements: negative index (there is no wrap-around)")
+        indices = np.ascontiguousarray(indices, dtype=np.uint64)
+        grid = self.chunk_grid_shape()
+        n_grid = int(np.prod(grid))
+        ptrs = (C.c_void_p * n_grid)()
+        lens = (C.c_uint64 * n_grid)()
+        keep = [indices]
+        for lin in L.points_chunks(self.shape, self.chunk_shape, indices):
+            self._lookup(np.unravel_index(lin, grid), lin, ptrs, lens, keep)
+        return indices.ctypes.data, int(indices.shape[0]), False, ptrs, lens, keep
+
+    def retrieve_elements(self, indices, out=None, _cache=None):
+        """The elements at a list of coordinates (Indexer for &[ArrayIndices], zarrs_chunk_grid/src/
+        indexer.rs:285-392; zgpu_retrieve_elements): each touched chunk, or inner chunk of a shard, is
+        decoded once on the GPU and the elements are gathered in HBM. indices: an (n, ndim) integer
+        array or a tuple of ndim 1-D arrays, numpy or torch (see _point_tables); duplicates are
+        allowed; a negative or out-of-bounds coordinate raises ZgpuError(INVALID_ARGUMENT). out: a
+        contiguous numpy array or device tensor of n elements of the array's element size; without it a
+        numpy array is returned."""
+        ip, n, idev, ptrs, lens, keep = self._point_tables(indices)
+        if out is None:
+            out = np.empty(n, dtype=self.dtype)
+        if int(np.prod(out.shape)) != n:
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"retrieve_elements: out of {int(np.prod(out.shape))} elements, {n} points")
+        # the library writes n elements of the array's element size back to back
+        if isinstance(out, np.ndarray):
+            fits = out.dtype.itemsize == self.dtype.itemsize and out.flags.c_contiguous
+        else:
+            fits = out.element_size() == self.dtype.itemsize and out.is_contiguous()
+        if not fits:
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"retrieve_elements: out must be contiguous with elements of "
+                                                  f"{self.dtype.itemsize} bytes")
+        odev, op = _out_ptr(out)
+        flags = (L.ENC_DEVICE if self.store.device else 0) | (L.OUT_DEVICE if odev else 0) | \
+            (L.IDX_DEVICE if idev else 0) | (0 if self._validate else L.NO_VALIDATE)
+        args = (self.codecs._h, self.ndim, L.u64s(self.shape), L.u64s(self.chunk_shape), ptrs, lens, ip, n, op,
+                flags, default_stream(None, out, *keep))
+        if _cache is not None:
+            rc = L.load().zgpu_cache_retrieve_elements(_cache._h, *args)
+        else:
+            rc = L.load().zgpu_retrieve_elements(*args)
+        del keep
+        L.check(rc)
+        return out
 
     def retrieve_array_subset_into(self, start, shape, out) -> None:
         if isinstance(self.store, FilesystemStore):
@@ -465,6 +553,11 @@ class ArrayCached:
 
     def retrieve_array_subset_dlpack(self, start=None, shape=None):
         return self.array.retrieve_array_subset_dlpack(start, shape, cache=self.cache)
+
+    def retrieve_elements(self, indices, out=None):
+        """Array.retrieve_elements through the cache (zgpu_cache_retrieve_elements): the touched chunks
+        that miss are decoded whole into the cache, the elements gathered from it."""
+        return self.array.retrieve_elements(indices, out, _cache=self.cache)
 
     def retrieve_chunk(self, idx) -> np.ndarray:
         a = self.array

@@ -27,6 +27,7 @@
 #include "../../include/zgpu.h"
 #include "chain.hpp"
 #include "internal.hpp"
+#include "points.hpp"
 
 using namespace zgpu;
 
@@ -118,7 +119,117 @@ int bind(zgpu_cache &K, const zgpu_chain *ch, uint32_t nd, const uint64_t *chunk
   return ZGPU_OK;
 }
 
+// The chunks of a read (lins) against the map: a hit moves to the front of the LRU list, a chunk whose key
+// is missing is cached as "no chunk", the others are the misses to decode (need: their positions in lins).
+// Returns how many of the read's chunks hold or need a slot.
+uint64_t lookup(zgpu_cache &K, const std::vector<uint64_t> &lins, const void *const *chunk_ptrs,
+                std::vector<size_t> &need) {
+  uint64_t present = 0;
+  for (size_t k = 0; k < lins.size(); k++) {
+    const uint64_t lin = lins[k];
+    auto e = K.map.find(lin);
+    if (e != K.map.end()) {
+      K.lru.splice(K.lru.begin(), K.lru, e->second.it);
+      K.hits++;
+      if (e->second.slot >= 0) present++;
+      continue;
+    }
+    K.misses++;
+    if (chunk_ptrs[lin]) {
+      need.push_back(k);
+      present++;
+    } else {  // missing key: cached as "no chunk" (fill value)
+      K.lru.push_front(lin);
+      K.map[lin] = zgpu_cache::Entry{-1, K.lru.begin()};
+      K.n_slotless++;
+    }
+  }
+  K.trim_slotless(lins);
+  return present;
+}
+
+// A slot for a miss: a free one, else that of the least recently used entry the read does not use (-1: none).
+int64_t take_slot(zgpu_cache &K, const std::unordered_map<uint64_t, char> &in_read) {
+  if (!K.free_slots.empty()) {
+    const int64_t slot = (int64_t)K.free_slots.back();
+    K.free_slots.pop_back();
+    return slot;
+  }
+  for (auto it = K.lru.end(); it != K.lru.begin();) {
+    --it;
+    const uint64_t victim = *it;
+    if (in_read.count(victim)) continue;
+    auto ve = K.map.find(victim);
+    if (ve->second.slot < 0) continue;  // holds no slot
+    const int64_t slot = ve->second.slot;
+    K.lru.erase(it);
+    K.map.erase(ve);
+    return slot;
+  }
+  return -1;
+}
+
+// The decoded misses become entries; the slot of one that failed goes back (the error is the call's).
+void commit(zgpu_cache &K, const std::vector<uint64_t> &lins, const std::vector<size_t> &need,
+            const std::vector<int64_t> &mslot, const int32_t *st) {
+  for (size_t j = 0; j < need.size(); j++) {
+    if (st[j] != 0) {
+      K.free_slots.push_back((uint64_t)mslot[j]);
+      continue;
+    }
+    const uint64_t lin = lins[need[j]];
+    K.lru.push_front(lin);
+    K.map[lin] = zgpu_cache::Entry{mslot[j], K.lru.begin()};
+  }
+}
 }  // namespace
+
+// The cache's half of a read by coordinates (points.hpp): the same lookup, slots and commit as a subset
+// read, with the decode and the gather left to points.cpp, which runs them on its own stream.
+int zgpu::cache_points_begin(zgpu_cache *K, zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape,
+                             const std::vector<uint64_t> &lins, const void *const *chunk_ptrs, CachePoints &P) {
+  P.lock = std::unique_lock<std::mutex>(K->mu);
+  if (const int rc = bind(*K, ch, nd, chunk_shape)) return rc;
+  const uint64_t present = lookup(*K, lins, chunk_ptrs, P.need);
+  P.direct = present > K->n_slots;
+  if (P.direct) {
+    P.lock.unlock();
+    return ZGPU_OK;
+  }
+  std::unordered_map<uint64_t, char> in_read;
+  if (!P.need.empty())
+    for (uint64_t lin : lins) in_read[lin] = 1;
+  P.cache = K;
+  for (size_t k = 0; k < P.need.size(); k++) {
+    const int64_t slot = take_slot(*K, in_read);
+    if (slot < 0) return fail(ZGPU_INVALID_ARGUMENT, "zgpu_cache: no slot could be freed");  // (~CachePoints)
+    P.need_slot.push_back(slot);
+  }
+  P.pool = K->pool;
+  P.slot_bytes = K->slot_bytes;
+  P.n_slots = K->n_slots;
+  return ZGPU_OK;
+}
+
+void zgpu::cache_points_commit(zgpu_cache *K, CachePoints &P, const std::vector<uint64_t> &lins, const int32_t *st) {
+  commit(*K, lins, P.need, P.need_slot, st);
+  P.committed = true;
+}
+
+zgpu::CachePoints::~CachePoints() {
+  if (!cache || committed || !lock.owns_lock()) return;
+  for (int64_t sl : need_slot) cache->free_slots.push_back((uint64_t)sl);  // undecoded: free again
+}
+
+void zgpu::cache_points_slots(zgpu_cache *K, const std::vector<uint64_t> &lins, std::vector<int64_t> &slot) {
+  slot.assign(lins.size(), -2);
+  for (size_t k = 0; k < lins.size(); k++) {
+    auto e = K->map.find(lins[k]);
+    if (e != K->map.end()) slot[k] = e->second.slot;
+  }
+}
+
+zgpu_ctx *zgpu::cache_ctx(const zgpu_cache *K) { return K->ctx; }
 
 extern "C" {
 
@@ -181,27 +292,7 @@ int zgpu_cache_retrieve_array_subset(zgpu_cache *K, zgpu_chain *ch, uint32_t nd,
   if ((rc = bind(*K, ch, nd, chunk_shape))) return rc;
   // the chunks this read needs that hold no slot yet
   std::vector<size_t> need;
-  uint64_t present = 0;
-  for (size_t k = 0; k < descs.size(); k++) {
-    const uint64_t lin = lins[k];
-    auto e = K->map.find(lin);
-    if (e != K->map.end()) {
-      K->lru.splice(K->lru.begin(), K->lru, e->second.it);
-      K->hits++;
-      if (e->second.slot >= 0) present++;
-      continue;
-    }
-    K->misses++;
-    if (chunk_ptrs[lin]) {
-      need.push_back(k);
-      present++;
-    } else {  // missing key: cached as "no chunk" (fill value)
-      K->lru.push_front(lin);
-      K->map[lin] = zgpu_cache::Entry{-1, K->lru.begin()};
-      K->n_slotless++;
-    }
-  }
-  K->trim_slotless(lins);
+  const uint64_t present = lookup(*K, lins, chunk_ptrs, need);
   if (present > K->n_slots) {  // the read alone exceeds the capacity: decode it directly, cache nothing new
     return zgpu_retrieve_array_subset(ch, nd, array_shape, chunk_shape, chunk_ptrs, chunk_lens, sel_start, sel_shape,
                                       out, flags, hip_stream);
@@ -214,23 +305,7 @@ int zgpu_cache_retrieve_array_subset(zgpu_cache *K, zgpu_chain *ch, uint32_t nd,
     std::vector<zgpu_chunk_desc> md;
     std::vector<int64_t> mslot;
     for (size_t k : need) {
-      int64_t slot = -1;
-      if (!K->free_slots.empty()) {
-        slot = (int64_t)K->free_slots.back();
-        K->free_slots.pop_back();
-      } else {
-        for (auto it = K->lru.end(); it != K->lru.begin();) {
-          --it;
-          const uint64_t victim = *it;
-          if (in_read.count(victim)) continue;
-          auto ve = K->map.find(victim);
-          if (ve->second.slot < 0) continue;  // holds no slot
-          slot = ve->second.slot;
-          K->lru.erase(it);
-          K->map.erase(ve);
-          break;
-        }
-      }
+      const int64_t slot = take_slot(*K, in_read);
       if (slot < 0) return fail(ZGPU_INVALID_ARGUMENT, "zgpu_cache: no slot could be freed");
       zgpu_chunk_desc d{};
       d.enc = chunk_ptrs[lins[k]];
@@ -260,15 +335,7 @@ int zgpu_cache_retrieve_array_subset(zgpu_cache *K, zgpu_chain *ch, uint32_t nd,
       for (int64_t sl : mslot) K->free_slots.push_back((uint64_t)sl);
       return rc;
     }
-    for (size_t j = 0; j < need.size(); j++) {
-      if (st[j] != 0) {  // not cached; the error is the call's
-        K->free_slots.push_back((uint64_t)mslot[j]);
-        continue;
-      }
-      const uint64_t lin = lins[need[j]];
-      K->lru.push_front(lin);
-      K->map[lin] = zgpu_cache::Entry{mslot[j], K->lru.begin()};
-    }
+    commit(*K, lins, need, mslot, st.data());
     if (rc) return fail(rc, zgpu_status_name(rc));
   }
   // gather the subset from the cached chunks (device-resident, decoded): one batch

@@ -257,6 +257,29 @@ struct ZgOverlayBox {
 hipError_t launch_subset_overlay(const ZgOverlayBox *boxes, const uint64_t *rows, uint32_t n_boxes, uint64_t n_rows,
                                  uint32_t nd, uint32_t es, hipStream_t s);
 
+// ---- read by coordinates (kernels/points.hip) ----
+// n points of nd u64 coordinates each. A point's leaf key is sum(coord[d] / leaf_shape[d] * key_stride[d])
+// (the C-order linear index in the array-wide leaf grid), its element's offset inside the decoded leaf
+// sum(coord[d] % leaf_shape[d] * leaf_stride[d]) (C order of leaf_shape).
+struct ZgPoints {
+  uint64_t n;
+  uint32_t nd, pad;
+  uint64_t array_shape[ZG_MAXD], leaf_shape[ZG_MAXD], key_stride[ZG_MAXD], leaf_stride[ZG_MAXD];
+  alignas(8) uint8_t fill[16];
+};
+// entries of k_points_gather's per-slot source table that are no address
+#define ZG_POINTS_SKIP 0ull  // the slot's leaf is not staged in this round: its points are left alone
+#define ZG_POINTS_FILL 1ull  // the leaf's chunk key is missing: its points read the fill value
+// wide: 64-bit divisions (an extent of the array or of the leaf, or the number of keys, does not fit 32 bits:
+// PointsGeom::wide, never decided anywhere else). bitmap: one bit per
+// key, zeroed; *oob: UINT64_MAX, receives the smallest out-of-bounds point index.
+hipError_t launch_points_mark(const uint64_t *idx, const ZgPoints &P, bool wide, uint32_t *bitmap, uint64_t *oob,
+                              hipStream_t s);
+// prefix[w]: set bits of the bitmap's words before w; src[slot]: ZG_POINTS_*, or the slot's decoded leaf
+// (aligned to min(es, 8)); out: n elements of es bytes (1, 2, 4, 8 or 16), aligned to min(es, 8).
+hipError_t launch_points_gather(const uint64_t *idx, const ZgPoints &P, bool wide, uint32_t es, const uint32_t *bitmap,
+                                const uint32_t *prefix, const uint64_t *src, uint8_t *out, hipStream_t s);
+
 // The value codecs and packbits (kernels/value.hip). vt_*: ZgValueType of the encoded / decoded
 // elements, VT_I8..VT_F64; through_f32: `astype` was given, so the cast between the two types runs (through
 // f32, cast_array) even when they are equal; without it they must be equal. in and out hold n elements
