@@ -39,6 +39,9 @@
  *                          array_write_ops_array.rs:183-208), store_chunk_subset_with_options
  *                          (array_update_ops_array.rs:152-210) and, inside a shard, the inner-chunk
  *                          update of sharding/sharding_partial_encoder.rs
+ *   zgpu_store_elements <- ArrayPartialEncoderTraits::partial_encode(&dyn Indexer, bytes) for a list of
+ *                          coordinates: CodecPartialDefault (zarrs_codec/src/codec_partial_default.rs:
+ *                          324-380) with update_array_bytes_indexer (zarrs_codec/src/array_bytes.rs:685-726)
  *   status codes        <- CodecError variants (zarrs_codec/src/lib.rs:617-686), 1:1 (see below).
  *
  * Threading: every entry point is thread-safe. Calls on one context run concurrently: each takes one
@@ -616,6 +619,48 @@ int zgpu_store_array_subset(zgpu_chain *chain, uint32_t ndim, const uint64_t *ar
  * whichever side enc is on) before the result is released: for stores that keep buffers of their own.
  * Synchronous on hip_stream. */
 int zgpu_store_entry_copy(zgpu_chain *chain, const zgpu_store_entry *entry, void *dst, void *hip_stream);
+/*
+ * The store by coordinates: ArrayPartialEncoderTraits::partial_encode(indexer, bytes) for a list of
+ * ArrayIndices. data[i] (n native-endian elements) becomes the element at indices[i] ([n][ndim] uint64,
+ * row-major, 8-byte aligned). A coordinate that appears more than once takes the value of the point with
+ * the HIGHEST i: for an unsharded chunk zarrs serves the call by CodecPartialDefault (zarrs_codec/src/
+ * codec_partial_default.rs:324-380: decode, update_array_bytes, encode), and update_array_bytes_indexer
+ * (zarrs_codec/src/array_bytes.rs:685-726) copies the update elements in indexer order, so the last one
+ * stays; the result here is exactly that. For sharding_indexed the reference has no such path yet
+ * (sharding/sharding_partial_encoder.rs:196-201, "does not yet support partial encoding with generic
+ * indexers"); the result here is what zarrs gives when the points are stored one after another, in
+ * order, as one-element subsets through its box path, i.e. the inner-chunk update zgpu_store_array_subset
+ * implements.
+ * Chains: exactly those zgpu_store_array_subset accepts, with the same refusals (ZGPU_UNSUPPORTED before
+ * any GPU work); the granule is the same leaf chunk. EVERY touched leaf is treated as partly covered:
+ * its old bytes are decoded in full, once, all touched leaves in one batch (checksums as for
+ * zgpu_store_array_subset; a missing key or an absent inner chunk reads as the fill value), the points
+ * are scattered into the decoded leaves in HBM (k_points_claim: per element the highest i;
+ * k_points_scatter: the winners write), and from there everything is zgpu_store_array_subset's: the fill
+ * check, the encode of what is not all fill, the shard layout with untouched inner chunks carried byte
+ * for byte, the erasure of a leaf or shard left all fill or empty, ZGPU_STORE_EMPTY_CHUNKS.
+ * chunk_ptrs / chunk_lens: as for zgpu_retrieve_elements; only the chunks the points touch are read
+ * (zgpu_points_chunks tells which). *entries: one entry per chunk that holds a touched leaf, in C order of
+ * the chunk grid; a failing chunk carries its status and no action (its points are dropped), the others
+ * are valid; the call returns the first non-zero status. Lifetimes as for zgpu_store_array_subset.
+ * flags: ZGPU_ENC_DEVICE: old chunks and entries' enc are device memory; ZGPU_OUT_DEVICE: `data` is
+ * device memory, aligned to min(element size, 8); ZGPU_IDX_DEVICE: indices is device memory;
+ * ZGPU_NO_VALIDATE, ZGPU_STORE_EMPTY_CHUNKS. One path: host indices and data are uploaded first.
+ * A point out of bounds fails the whole call with ZGPU_INVALID_ARGUMENT before anything is decoded (found
+ * by k_points_mark; the message names the smallest such point and its axis; *entries NULL). There is no
+ * per-point status. n == 0: ZGPU_OK, no entries, no result. Element sizes 1, 2, 4, 8 and 16. Limits,
+ * ZGPU_UNSUPPORTED with a message that says so, before any device work: the bitmap of one bit per leaf
+ * (ZGPU_POINTS_BITMAP_MAX_BYTES, as for the read), and n >= 2^32 - 1 (the winner table holds i + 1 in 32
+ * bits). All touched leaves are staged at once (no rounds, unlike the read): decoded leaf bytes plus 4
+ * bytes of winner table per staged element; when that allocation fails the message gives both figures.
+ * Counters: ZGPU_CTR_POINT_LEAVES, ZGPU_CTR_STORE_DECODED / _ENCODED / _CARRIED. Synchronous on
+ * hip_stream. No locking, and no cache is invalidated.
+ */
+int zgpu_store_elements(zgpu_chain *chain, uint32_t ndim, const uint64_t *array_shape,
+                        const uint64_t *chunk_shape, const void *const *chunk_ptrs, const uint64_t *chunk_lens,
+                        const void *indices, uint64_t n, const void *data, uint32_t flags,
+                        const zgpu_store_entry **entries, uint64_t *n_entries, zgpu_result **result,
+                        void *hip_stream);
 /*
  * The host's classification behind zgpu_store_array_subset, without a device: the chunks the subset
  * meets in C order of the chunk grid (chunks[k]: linear index) and, per chunk, the class of each of its

@@ -44,6 +44,26 @@ pub trait ArrayGpuExt {
     /// # Errors
     /// Returns [`ArrayError`] as [`ArrayGpuExt::retrieve_array_subset_gpu`] does.
     fn retrieve_array_subset_gpu_multi(&self, subset: &ArraySubset, devices: &[i32]) -> Result<Vec<u8>, ArrayError>;
+
+    /// The store by coordinates (`zgpu_store_elements`): `data[i]` (native-endian element bytes, `n` elements
+    /// back to back) becomes the element at `indices[i]` (`n * ndim` coordinates, row-major); of several
+    /// points on one coordinate the last one wins (update_array_bytes_indexer, zarrs_codec/src/
+    /// array_bytes.rs:685-726). Every touched chunk, or inner chunk of a shard, is decoded once on the GPU,
+    /// the points are scattered in HBM and the touched leaves are encoded again. Nothing is written: the
+    /// call returns, in chunk-grid order, what every chunk holding a touched leaf becomes --
+    /// `(chunk indices, Some(encoded bytes))` to store with `Array::store_encoded_chunk`, or
+    /// `(chunk indices, None)` to erase with `Array::erase_chunk` -- and returns an error, with no
+    /// entries, if any chunk failed or a point is out of bounds. No chunk cache is invalidated.
+    ///
+    /// # Errors
+    /// Returns [`ArrayError`] on storage errors, unsupported chains (those `zgpu_store_array_subset`
+    /// refuses), an out-of-bounds point, or the first failing chunk's status.
+    fn store_elements_gpu(
+        &self,
+        indices: &[u64],
+        data: &[u8],
+        store_empty_chunks: bool,
+    ) -> Result<Vec<(Vec<u64>, Option<Vec<u8>>)>, ArrayError>;
 }
 
 fn gpu_chain<TStorage: ?Sized + ReadableStorageTraits + 'static>(array: &Array<TStorage>) -> Result<Chain, ArrayError> {
@@ -224,6 +244,116 @@ impl<TStorage: ?Sized + ReadableStorageTraits + 'static> ArrayGpuExt for Array<T
                 0,
             )
         };
+        if rc != ffi::ZGPU_OK {
+            return Err(status_error(rc).into());
+        }
+        Ok(out)
+    }
+
+    fn store_elements_gpu(
+        &self,
+        indices: &[u64],
+        data: &[u8],
+        store_empty_chunks: bool,
+    ) -> Result<Vec<(Vec<u64>, Option<Vec<u8>>)>, ArrayError> {
+        let nd = self.dimensionality();
+        if nd == 0 || nd > ffi::ZGPU_MAX_DIMS {
+            return Err(CodecError::Other(format!("zarrs_gpu: unsupported dimensionality {nd}")).into());
+        }
+        let es = self
+            .data_type()
+            .fixed_size()
+            .ok_or_else(|| CodecError::Other("zarrs_gpu: fixed-size data types only".into()))?;
+        if indices.len() % nd != 0 || data.len() != indices.len() / nd * es {
+            return Err(CodecError::Other("zarrs_gpu: store_elements takes n * ndim coordinates and n elements".into()).into());
+        }
+        let n = (indices.len() / nd) as u64;
+        let chain = gpu_chain(self)?;
+        let chunk_shape: Vec<u64> = self.chunk_shape(&vec![0; nd])?.iter().map(|c| c.get()).collect();
+        let grid: Vec<u64> = self.chunk_grid_shape().to_vec();
+        // only the chunks the points touch are fetched (zgpu_points_chunks: two-call sizing)
+        let mut n_chunks = 0u64;
+        let mut lins: Vec<u64> = Vec::new();
+        for _ in 0..2 {
+            lins.resize(usize::try_from(n_chunks).map_err(|e| CodecError::Other(e.to_string()))?, 0);
+            // SAFETY: shapes of nd entries, n * nd coordinates, `lins` of the capacity passed.
+            let rc = unsafe {
+                ffi::zgpu_points_chunks(
+                    nd as u32,
+                    self.shape().as_ptr(),
+                    chunk_shape.as_ptr(),
+                    indices.as_ptr(),
+                    n,
+                    lins.as_mut_ptr(),
+                    lins.len() as u64,
+                    &mut n_chunks,
+                )
+            };
+            if rc != ffi::ZGPU_OK {
+                return Err(status_error(rc).into());
+            }
+        }
+        let unravel = |lin: u64| -> Vec<u64> {
+            let mut idx = vec![0u64; nd];
+            let mut rem = lin;
+            for d in (0..nd).rev() {
+                idx[d] = rem % grid[d];
+                rem /= grid[d];
+            }
+            idx
+        };
+        let mut bufs = Vec::new();
+        let mut have = Vec::new();
+        for &lin in &lins {
+            if let Some(b) = self.retrieve_encoded_chunk(&unravel(lin))? {
+                have.push(lin);
+                bufs.push(b);
+            }
+        }
+        let n_grid = usize::try_from(grid.iter().product::<u64>()).map_err(|e| CodecError::Other(e.to_string()))?;
+        let (ptrs, lens) = grid_tables(n_grid, &bufs, &have);
+        let mut entries: *const ffi::zgpu_store_entry = std::ptr::null();
+        let mut n_entries = 0u64;
+        let mut result: *mut ffi::zgpu_result = std::ptr::null_mut();
+        let flags = if store_empty_chunks { ffi::ZGPU_STORE_EMPTY_CHUNKS } else { 0 };
+        // SAFETY: the tables, shapes, host chunk buffers, indices and data outlive the synchronous call.
+        let rc = unsafe {
+            ffi::zgpu_store_elements(
+                chain.as_ptr(),
+                nd as u32,
+                self.shape().as_ptr(),
+                chunk_shape.as_ptr(),
+                ptrs.as_ptr(),
+                lens.as_ptr(),
+                indices.as_ptr().cast(),
+                n,
+                data.as_ptr().cast(),
+                flags,
+                &mut entries,
+                &mut n_entries,
+                &mut result,
+                std::ptr::null_mut(),
+            )
+        };
+        let mut out = Vec::new();
+        if rc == ffi::ZGPU_OK && !entries.is_null() {
+            // SAFETY: n_entries entries, valid with their host bytes until the result is released below.
+            for e in unsafe { std::slice::from_raw_parts(entries, n_entries as usize) } {
+                let bytes = (e.action == ffi::ZGPU_STORE_SET).then(|| {
+                    if e.enc_len == 0 {
+                        Vec::new()
+                    } else {
+                        // SAFETY: enc holds enc_len host bytes (no ZGPU_ENC_DEVICE).
+                        unsafe { std::slice::from_raw_parts(e.enc.cast::<u8>(), e.enc_len as usize) }.to_vec()
+                    }
+                });
+                out.push((unravel(e.chunk), bytes));
+            }
+        }
+        if !result.is_null() {
+            // SAFETY: the result of the call above, released once.
+            unsafe { ffi::zgpu_result_release(result) };
+        }
         if rc != ffi::ZGPU_OK {
             return Err(status_error(rc).into());
         }

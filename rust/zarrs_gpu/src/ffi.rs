@@ -32,7 +32,7 @@ pub const ZGPU_ZSTD_LITS_FIRST: u32 = 0x40;
 pub const ZGPU_COALESCE: u32 = 0x20;
 /// zgpu_store_array_subset: store chunks that equal the fill value everywhere (not bound here yet).
 pub const ZGPU_STORE_EMPTY_CHUNKS: u32 = 0x80;
-/// zgpu_retrieve_elements: `indices` is device memory.
+/// zgpu_retrieve_elements / zgpu_store_elements: `indices` is device memory.
 pub const ZGPU_IDX_DEVICE: u32 = 0x100;
 /// zgpu_retrieve_elements: the dense bitmap of one bit per leaf of the array may not pass this size.
 pub const ZGPU_POINTS_BITMAP_MAX_BYTES: u64 = 16 << 20;
@@ -76,6 +76,24 @@ pub const ZGPU_CTR_STORE_CARRIED: usize = 11;
 pub const ZGPU_CTR_POINT_LEAVES: usize = 12;
 pub const ZGPU_CTR_POINT_ROUNDS: usize = 13;
 pub const ZGPU_N_COUNTERS: usize = 14;
+
+/// zgpu_store_entry.action
+pub const ZGPU_STORE_SET: u32 = 1;
+pub const ZGPU_STORE_ERASE: u32 = 2;
+
+/// zgpu_store_entry: what one chunk of a store becomes (valid until zgpu_result_release of the call's result).
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct zgpu_store_entry {
+    /// C-order linear chunk-grid index
+    pub chunk: u64,
+    /// ZGPU_STORE_SET / ZGPU_STORE_ERASE; 0 when status != 0
+    pub action: u32,
+    pub status: c_int,
+    /// ZGPU_STORE_SET: the chunk's new encoded bytes
+    pub enc: *const c_void,
+    pub enc_len: u64,
+}
 
 /// zgpu_encode_desc: one chunk of a device-resident array encoded into `dst`.
 #[repr(C)]
@@ -273,6 +291,26 @@ unsafe extern "C" {
         n: u64,
         out: *mut c_void,
         flags: u32,
+        hip_stream: *mut c_void,
+    ) -> c_int;
+    /// ArrayPartialEncoderTraits::partial_encode for a list of coordinates (codec_partial_default.rs:324-380,
+    /// update_array_bytes_indexer, zarrs_codec/src/array_bytes.rs:685-726) on the GPU: data[i] becomes the
+    /// element at indices[i] ([n][ndim] u64; device memory with ZGPU_IDX_DEVICE), the last of several points
+    /// on one coordinate wins. One entry per chunk holding a touched leaf.
+    pub fn zgpu_store_elements(
+        chain: *mut zgpu_chain,
+        ndim: u32,
+        array_shape: *const u64,
+        chunk_shape: *const u64,
+        chunk_ptrs: *const *const c_void,
+        chunk_lens: *const u64,
+        indices: *const c_void,
+        n: u64,
+        data: *const c_void,
+        flags: u32,
+        entries: *mut *const zgpu_store_entry,
+        n_entries: *mut u64,
+        result: *mut *mut zgpu_result,
         hip_stream: *mut c_void,
     ) -> c_int;
 }

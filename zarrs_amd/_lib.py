@@ -47,13 +47,14 @@ EXPORTS = [
     "zgpu_group_algorithmic_bytes", "zgpu_group_counters", "zgpu_group_destroy", "zgpu_plan_scatter_path",
     "zgpu_store_array_subset", "zgpu_store_entry_copy", "zgpu_store_classify",
     "zgpu_points_chunks", "zgpu_points_geometry", "zgpu_retrieve_elements", "zgpu_cache_retrieve_elements",
+    "zgpu_store_elements",
 ]
 SCATTER_ROWS, SCATTER_TILED, SCATTER_GENERIC, SCATTER_TILED_PERSISTENT = range(4)  # zgpu_plan_scatter_path
 CTR_ENC_BYTES, CTR_ZSTD_SERIAL, CTR_ZSTD_PARALLEL, CTR_BLOSC_RERUN, CTR_BLOSC_BLOCKS, CTR_ITEMS, \
     CTR_ZSTD_LATENCY, CTR_BZ2_BLOCKS, CTR_BZ2_ROUNDS, CTR_STORE_DECODED, CTR_STORE_ENCODED, \
     CTR_STORE_CARRIED, CTR_POINT_LEAVES, CTR_POINT_ROUNDS = range(14)
 N_COUNTERS = 14
-IDX_DEVICE = 0x100  # zgpu_retrieve_elements flag: the indices are device memory
+IDX_DEVICE = 0x100  # zgpu_retrieve_elements / zgpu_store_elements flag: the indices are device memory
 POINTS_BITMAP_MAX_BYTES = 16 << 20  # zgpu_retrieve_elements: one bit per leaf of the array
 STORE_EMPTY_CHUNKS = 0x80  # zgpu_store_array_subset flag
 STORE_SET, STORE_ERASE = 1, 2  # zgpu_store_entry.action
@@ -214,6 +215,8 @@ def load() -> C.CDLL:
     L.zgpu_store_array_subset.argtypes = [vp, u32, P64, P64, C.POINTER(vp), P64, P64, P64, vp, u32,
                                           C.POINTER(C.POINTER(StoreEntry)), P64, C.POINTER(vp), vp]
     L.zgpu_store_entry_copy.argtypes = [vp, C.POINTER(StoreEntry), vp, vp]
+    L.zgpu_store_elements.argtypes = [vp, u32, P64, P64, C.POINTER(vp), P64, vp, u64, vp, u32,
+                                      C.POINTER(C.POINTER(StoreEntry)), P64, C.POINTER(vp), vp]
     L.zgpu_store_classify.argtypes = [u32, P64, P64, P64, P64, P64, P64, C.POINTER(C.c_uint8), u64, P64]
     L.zgpu_points_chunks.argtypes = [u32, P64, P64, vp, u64, P64, u64, P64]
     L.zgpu_points_geometry.argtypes = [u32, P64, P64, P64, P64, C.POINTER(u32)]

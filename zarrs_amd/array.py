@@ -210,10 +210,10 @@ class Array:
             ptrs[lin] = b.ctypes.data
             lens[lin] = len(v)
 
-    def _point_tables(self, indices):
-        """(pointer to the indices, n, on the device, pointer tables, what to keep alive) of a read by
-        coordinates. indices: an (n, ndim) integer array (numpy, or a torch tensor; a list of points is
-        read as such an array) or a tuple of ndim 1-D arrays. Device indices over a DeviceStore stay on the device, and every chunk's pointer goes
+    def _point_tables(self, indices, what="retrieve_elements"):
+        """(pointer to the indices, n, on the device, pointer tables, what to keep alive) of a read or a
+        store by coordinates (`what` leads the messages). indices: an (n, ndim) integer array (numpy, or a
+        torch tensor; a list of points is read as such an array) or a tuple of ndim 1-D arrays. Device indices over a DeviceStore stay on the device, and every chunk's pointer goes
         into the tables; otherwise the indices go through the host, where zgpu_points_chunks selects
         the keys to fetch."""
         nd = self.ndim
@@ -224,7 +224,7 @@ class Array:
         is_t = lambda v: torch is not None and isinstance(v, torch.Tensor)  # noqa: E731
         if isinstance(indices, tuple):  # (a list is a list of points, as numpy reads it)
             if len(indices) != nd or not all(hasattr(v, "shape") for v in indices):
-                raise L.ZgpuError(L.INVALID_ARGUMENT, f"retrieve_elements: {len(indices)} index arrays, rank {nd}")
+                raise L.ZgpuError(L.INVALID_ARGUMENT, f"{what}: {len(indices)} index arrays, rank {nd}")
             if all(is_t(v) and v.is_cuda for v in indices):
                 indices = torch.stack([v.reshape(-1) for v in indices], dim=1)
             else:
@@ -232,10 +232,10 @@ class Array:
         if is_t(indices) and indices.is_cuda and self.store.device:
             if indices.dtype not in (torch.int64, getattr(torch, "uint64", torch.int64)):
                 if indices.dtype.is_floating_point or indices.dtype == torch.bool:
-                    raise L.ZgpuError(L.INVALID_ARGUMENT, "retrieve_elements: indices must be integers")
+                    raise L.ZgpuError(L.INVALID_ARGUMENT, f"{what}: indices must be integers")
                 indices = indices.to(torch.int64)
             if indices.dim() != 2 or indices.shape[1] != nd:
-                raise L.ZgpuError(L.INVALID_ARGUMENT, f"retrieve_elements: indices of shape {list(indices.shape)}")
+                raise L.ZgpuError(L.INVALID_ARGUMENT, f"{what}: indices of shape {list(indices.shape)}")
             # (a negative int64 is a coordinate >= 2^63 to the bounds check: rejected there, no wrap-around)
             indices = indices.contiguous()
             ptrs, lens, keep = self._tables([0] * nd, self.shape)
@@ -246,11 +246,11 @@ class Array:
         if indices.size == 0:
             indices = indices.reshape(0, nd).astype(np.uint64)
         if indices.dtype.kind not in "iu":
-            raise L.ZgpuError(L.INVALID_ARGUMENT, "retrieve_elements: indices must be integers")
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"{what}: indices must be integers")
         if indices.ndim != 2 or indices.shape[1] != nd:
-            raise L.ZgpuError(L.INVALID_ARGUMENT, f"retrieve_elements: indices of shape {list(indices.shape)}")
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"{what}: indices of shape {list(indices.shape)}")
         if indices.dtype.kind == "i" and indices.size and int(indices.min()) < 0:
-            raise L.ZgpuError(L.INVALID_ARGUMENT, "retrieve_elements: negative index (there is no wrap-around)")
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"{what}: negative index (there is no wrap-around)")
         indices = np.ascontiguousarray(indices, dtype=np.uint64)
         grid = self.chunk_grid_shape()
         n_grid = int(np.prod(grid))
@@ -464,6 +464,10 @@ class Array:
         res = self.codecs.store_array_subset(self.shape, self.chunk_shape, ptrs, lens, start, data,
                                              bool(self.store.device), store_empty_chunks)
         del keep
+        return self._apply(res)
+
+    def _apply(self, res) -> list:
+        """The entries of a store call into the store, if every chunk succeeded; the result is released."""
         try:
             if res.rc:
                 raise L.ZgpuError(res.rc, L.last_error())
@@ -481,6 +485,40 @@ class Array:
             return done
         finally:
             res.release()
+
+    def store_elements(self, indices, data, store_empty_chunks: bool = False) -> list:
+        """The elements at a list of coordinates take `data` (ArrayPartialEncoderTraits::partial_encode
+        with an Indexer of coordinates: codec_partial_default.rs:324-380 and update_array_bytes_indexer,
+        zarrs_codec/src/array_bytes.rs:685-726; zgpu_store_elements): data[i] becomes the element at
+        indices[i]; of several points on one coordinate the LAST one wins. Each touched chunk, or inner
+        chunk of a shard, is decoded once on the GPU, the points are scattered into the decoded leaves
+        in HBM, and the leaves are encoded again (untouched inner chunks are carried byte for byte).
+        indices: as for retrieve_elements (host indices: only the touched keys are looked up; device
+        indices over a DeviceStore stay on the device and every chunk's pointer goes into the tables);
+        a negative or out-of-bounds coordinate raises ZgpuError(INVALID_ARGUMENT) and nothing is
+        written. data: n elements of the array's data type, numpy or torch, host or device.
+        The store is changed only if every chunk succeeded, as store_array_subset; there is no
+        per-point status. No locking, and an ArrayCached's cache is NOT invalidated: the caller clears
+        it after a store (there is no ArrayCached.store_elements).
+        Returns [(chunk key, L.STORE_SET or L.STORE_ERASE)] in chunk-grid order."""
+        ip, n, idev, ptrs, lens, keep = self._point_tables(indices, "store_elements")
+        if not hasattr(data, "shape"):
+            data = np.asarray(data)
+        if isinstance(data, np.ndarray):
+            data = np.ascontiguousarray(data, dtype=None if self.dtype.kind == "V" else self.dtype).reshape(-1)
+            fits = data.dtype.itemsize == self.dtype.itemsize
+        else:
+            data = data.contiguous().reshape(-1)
+            fits = data.element_size() == self.dtype.itemsize
+        if not fits or int(data.shape[0]) != n:
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"store_elements: data of {int(data.shape[0])} elements of "
+                                                  f"{data.dtype}, {n} points of {self.dtype.itemsize} bytes")
+        if isinstance(self.store, FilesystemStore) and getattr(data, "is_cuda", False):
+            data = data.cpu()  # host chunks in, host chunks out
+        res = self.codecs.store_elements(self.shape, self.chunk_shape, ptrs, lens, ip, n, idev, data,
+                                         bool(self.store.device), store_empty_chunks, self._validate, keep=keep)
+        del keep
+        return self._apply(res)
 
     def store_chunk(self, idx, data) -> list:
         """Array::store_chunk (array_write_ops_array.rs:183-208): chunk `idx` takes `data`, whose shape

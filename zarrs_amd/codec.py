@@ -335,6 +335,31 @@ class CodecChain:
             raise L.ZgpuError(rc, L.last_error())
         return StoreResult(self, rc, ents, n.value, res, enc_device)
 
+    def store_elements(self, array_shape, chunk_shape, ptrs, lens, indices_ptr, n, idx_device: bool, data,
+                       enc_device: bool, store_empty_chunks: bool = False, validate_checksums: bool = True,
+                       stream=None, keep=()) -> "StoreResult":
+        """zgpu_store_elements: data[i] becomes the element at point i (indices_ptr: n x ndim uint64,
+        row-major, host or device memory as idx_device says; a coordinate given more than once takes
+        its last point's value). data: n elements, a contiguous numpy array or torch tensor, host or
+        device. ptrs / lens: the old encoded chunks by linear chunk-grid index. Returns the entries
+        (one per chunk holding a touched leaf) as store_array_subset does; a call-level error (an
+        out-of-bounds point, a refused chain) raises ZgpuError."""
+        dp, nbytes, ddev, dkeep = _ptr_len(data)
+        if nbytes != int(n) * self.dtype.itemsize:
+            raise L.ZgpuError(L.INVALID_ARGUMENT, f"store_elements: {nbytes} bytes of data for {int(n)} points of "
+                                                  f"{self.dtype.itemsize} bytes")
+        flags = (L.ENC_DEVICE if enc_device else 0) | (L.OUT_DEVICE if ddev else 0) | \
+            (L.IDX_DEVICE if idx_device else 0) | (L.STORE_EMPTY_CHUNKS if store_empty_chunks else 0) | \
+            (0 if validate_checksums else L.NO_VALIDATE)
+        ents, ne, res = C.POINTER(L.StoreEntry)(), C.c_uint64(), C.c_void_p()
+        rc = L.load().zgpu_store_elements(
+            self._h, len(array_shape), L.u64s(array_shape), L.u64s(chunk_shape), ptrs, lens, indices_ptr, int(n),
+            dp, flags, C.byref(ents), C.byref(ne), C.byref(res), default_stream(stream, data, *keep))
+        del dkeep
+        if rc and not res:
+            raise L.ZgpuError(rc, L.last_error())
+        return StoreResult(self, rc, ents, ne.value, res, enc_device)
+
     def partial_decode(self, encoded, shape, subset_start, subset_shape) -> np.ndarray:
         out = np.empty([int(s) for s in subset_shape], dtype=self.dtype)
         dev = _ptr_len(encoded)[2]

@@ -279,6 +279,17 @@ hipError_t launch_points_mark(const uint64_t *idx, const ZgPoints &P, bool wide,
 // (aligned to min(es, 8)); out: n elements of es bytes (1, 2, 4, 8 or 16), aligned to min(es, 8).
 hipError_t launch_points_gather(const uint64_t *idx, const ZgPoints &P, bool wide, uint32_t es, const uint32_t *bitmap,
                                 const uint32_t *prefix, const uint64_t *src, uint8_t *out, hipStream_t s);
+// The store by coordinates. dst[slot]: the slot's staged leaf (leaf_n elements of es bytes, aligned to
+// min(es, 8)), or ZG_POINTS_SKIP (its chunk's entry failed: its points are dropped). winner: one u32 per
+// staged element, [slot * leaf_n + offset], zeroed; P.n < 2^32 - 1.
+// claim: winner[...] = max(winner[...], i + 1) over the points i of that element (the last duplicate wins).
+hipError_t launch_points_claim(const uint64_t *idx, const ZgPoints &P, bool wide, uint64_t leaf_n, const uint32_t *bitmap,
+                               const uint32_t *prefix, const uint64_t *dst, uint32_t *winner, hipStream_t s);
+// scatter (after claim): point i writes data[i] (n elements of es bytes, aligned to min(es, 8)) into its
+// element of the staged leaf iff winner[...] == i + 1, with stores of the element's own width.
+hipError_t launch_points_scatter(const uint64_t *idx, const ZgPoints &P, bool wide, uint32_t es, uint64_t leaf_n,
+                                 const uint32_t *bitmap, const uint32_t *prefix, const uint64_t *dst,
+                                 const uint32_t *winner, const uint8_t *data, hipStream_t s);
 
 // The value codecs and packbits (kernels/value.hip). vt_*: ZgValueType of the encoded / decoded
 // elements, VT_I8..VT_F64; through_f32: `astype` was given, so the cast between the two types runs (through

@@ -20,7 +20,8 @@
 //      rounds. The cache decodes its misses into their slots instead and stages nothing;
 //   4. k_points_gather per round: key -> slot -> source address (a staged leaf, a cache slot, "fill value"
 //      or "not in this round"), one thread per point.
-// Every temporary is the call's Scratch's.
+// Every temporary is the call's Scratch's. Steps 1 and 2 (points_plan, points_mark, points_slots; points.hpp)
+// are also the front of the store by coordinates (zgpu_store_elements, store.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,11 +54,7 @@ uint64_t staging_budget() {
 
 constexpr int POINTS_DIRECT = -1;  // points_call with a cache: the read does not fit it, take the direct path
 
-struct Slot {
-  uint64_t lin, j;           // its chunk (C-order linear grid index), its index among the chunk's leaves
-  uint64_t origin[ZG_MAXD];  // the leaf's origin inside the chunk
-  size_t chunk;              // position of lin among the read's distinct chunks
-};
+using Slot = PointSlot;
 
 int points_call(zgpu_cache *K, zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const uint64_t *chunk_shape,
                 const void *const *chunk_ptrs, const uint64_t *chunk_lens, const void *indices, uint64_t n, void *out,
@@ -79,23 +76,16 @@ int points_call(zgpu_cache *K, zgpu_chain *ch, uint32_t nd, const uint64_t *arra
     composed_axes(top, nd, m);  // encoded axis a <-> decoded axis m[a]
     for (uint32_t a = 0; a < nd; a++) leaf_shape[m[a]] = top.a2b.inner_shape[a];
   }
-  PointsGeom G;
-  {
-    std::string err;
-    if (const int rc = points_geom(nd, array_shape, chunk_shape, leaf_shape, G, err)) return set_err(rc, err);
-  }
-  const uint64_t words = G.n_keys / 32 + (G.n_keys % 32 ? 1 : 0);
-  if (words > ZGPU_POINTS_BITMAP_MAX_BYTES / 4)
-    return set_err(ZGPU_UNSUPPORTED, "retrieve_elements: the array has " + std::to_string(G.n_keys) +
-                                         " leaves; the dense bitmap over them is limited to " +
-                                         std::to_string(ZGPU_POINTS_BITMAP_MAX_BYTES) + " bytes");
+  PointsFront F;
+  if (const int rc = points_plan("retrieve_elements", nd, array_shape, chunk_shape, leaf_shape, top.fill, indices, n, F))
+    return rc;
+  const PointsGeom &G = F.G;
+  const ZgPoints &P = F.P;
+  const uint64_t words = F.words;
   const bool enc_dev = flags & ZGPU_ENC_DEVICE, out_dev = flags & ZGPU_OUT_DEVICE, idx_dev = flags & ZGPU_IDX_DEVICE;
   const bool validate = ch->validate && !(flags & ZGPU_NO_VALIDATE);
-  if (n > (1ull << 56) / nd) return set_err(ZGPU_INVALID_ARGUMENT, "retrieve_elements: too many points");
   if (n && out_dev && (uintptr_t)out % std::min<uint32_t>(es, 8))
     return set_err(ZGPU_INVALID_ARGUMENT, "retrieve_elements: out is not aligned to its element size");
-  if (n && (uintptr_t)indices % 8)
-    return set_err(ZGPU_INVALID_ARGUMENT, "retrieve_elements: indices are not 8-byte aligned");
 
   HIPCHK(hipSetDevice(C->device));
   uint64_t *ctr = call_counters();
@@ -105,70 +95,19 @@ int points_call(zgpu_cache *K, zgpu_chain *ch, uint32_t nd, const uint64_t *arra
 
   // host tables the queued copies read: declared before the scratch, whose destructor waits for them
   std::vector<uint64_t> src_tab;
-  std::vector<uint32_t> prefix(words, 0);
+  std::vector<uint32_t> prefix;
   std::vector<zgpu_chunk_desc> descs;
   std::vector<Slot> slots;
   LaneScope ls(C);
   hipStream_t s = pick_stream(ls.L, stream);
   Scratch sc(C, s);
 
-  // 1. mark
-  const uint64_t *d_idx = (const uint64_t *)indices;
-  if (!idx_dev) {
-    uint64_t *d = sc.dev<uint64_t>(n * nd);
-    HIPCHK(hipMemcpyAsync(d, indices, n * nd * 8, hipMemcpyHostToDevice, s));
-    d_idx = d;
-  }
-  ZgPoints P{};
-  P.n = n;
-  P.nd = nd;
-  std::memcpy(P.fill, top.fill, sizeof(P.fill));
-  for (int d = (int)nd - 1; d >= 0; d--) {
-    P.array_shape[d] = array_shape[d];
-    P.leaf_shape[d] = leaf_shape[d];
-    P.key_stride[d] = d == (int)nd - 1 ? 1 : P.key_stride[d + 1] * G.leaf_grid[d + 1];
-    P.leaf_stride[d] = d == (int)nd - 1 ? 1 : P.leaf_stride[d + 1] * leaf_shape[d + 1];
-  }
-  // [out-of-bounds word | bitmap], cleared and read back together
-  const uint64_t mark_words = 1 + (words + 1) / 2;
-  uint64_t *d_mark = sc.dev<uint64_t>(mark_words), *h_mark = sc.pinned<uint64_t>(mark_words);
-  uint32_t *d_bitmap = (uint32_t *)(d_mark + 1);
-  HIPCHK(hipMemsetAsync(d_mark, 0xff, 8, s));
-  HIPCHK(hipMemsetAsync(d_bitmap, 0, (mark_words - 1) * 8, s));
-  HIPCHK(launch_points_mark(d_idx, P, G.wide, d_bitmap, d_mark, s));
-  HIPCHK(hipMemcpyAsync(h_mark, d_mark, mark_words * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (h_mark[0] != UINT64_MAX) {  // IndexerError::OutOfBounds: nothing was decoded, nothing written
-    const uint64_t i = h_mark[0];
-    uint64_t p[ZG_MAXD] = {};
-    if (i < n) {
-      if (idx_dev) {
-        HIPCHK(hipMemcpyAsync(p, d_idx + i * nd, nd * 8, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-      } else {
-        std::memcpy(p, (const uint64_t *)indices + i * nd, nd * 8);
-      }
-    }
-    for (uint32_t d = 0; d < nd; d++)
-      if (p[d] >= array_shape[d]) return set_err(ZGPU_INVALID_ARGUMENT, points_oob_message(i, d, p[d], array_shape[d]));
-    return set_err(ZGPU_INVALID_ARGUMENT, "point " + std::to_string(i) + " is out of bounds");
-  }
-
-  // 2. a slot per touched leaf, in key order; the read's distinct chunks
-  const uint32_t *bitmap = (const uint32_t *)(h_mark + 1);
+  // 1. mark; 2. a slot per touched leaf, in key order; the read's distinct chunks
+  if (const int rc = points_mark(sc, s, indices, idx_dev, F)) return rc;
+  const uint64_t *d_idx = F.d_idx;
+  const uint32_t *d_bitmap = F.d_bitmap;
   std::vector<uint64_t> lins;
-  for (uint64_t w = 0; w < words; w++) {
-    prefix[w] = (uint32_t)slots.size();
-    for (uint32_t v = bitmap[w]; v; v &= v - 1) {
-      Slot S{};
-      points_key_chunk(G, w * 32 + (uint64_t)__builtin_ctz(v), &S.lin, S.origin, &S.j);
-      slots.push_back(S);
-      if (lins.empty() || lins.back() != S.lin) lins.push_back(S.lin);
-    }
-  }
-  std::sort(lins.begin(), lins.end());
-  lins.erase(std::unique(lins.begin(), lins.end()), lins.end());
-  for (Slot &S : slots) S.chunk = (size_t)(std::lower_bound(lins.begin(), lins.end(), S.lin) - lins.begin());
+  points_slots(F, prefix, slots, lins);
   const uint64_t n_slots = slots.size();
 
   CachePoints CP;
@@ -326,6 +265,89 @@ int check_args(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const u
 }
 
 }  // namespace
+
+int zgpu::points_plan(const char *what, uint32_t nd, const uint64_t *array_shape, const uint64_t *chunk_shape,
+                      const uint64_t *leaf_shape, const uint8_t *fill, const void *indices, uint64_t n, PointsFront &F) {
+  PointsGeom &G = F.G;
+  {
+    std::string err;
+    if (const int rc = points_geom(nd, array_shape, chunk_shape, leaf_shape, G, err)) return set_err(rc, err);
+  }
+  F.words = G.n_keys / 32 + (G.n_keys % 32 ? 1 : 0);
+  if (F.words > ZGPU_POINTS_BITMAP_MAX_BYTES / 4)
+    return set_err(ZGPU_UNSUPPORTED, std::string(what) + ": the array has " + std::to_string(G.n_keys) +
+                                         " leaves; the dense bitmap over them is limited to " +
+                                         std::to_string(ZGPU_POINTS_BITMAP_MAX_BYTES) + " bytes");
+  if (n > (1ull << 56) / nd) return set_err(ZGPU_INVALID_ARGUMENT, std::string(what) + ": too many points");
+  if (n && (uintptr_t)indices % 8)
+    return set_err(ZGPU_INVALID_ARGUMENT, std::string(what) + ": indices are not 8-byte aligned");
+  ZgPoints &P = F.P;
+  P.n = n;
+  P.nd = nd;
+  std::memcpy(P.fill, fill, sizeof(P.fill));
+  for (int d = (int)nd - 1; d >= 0; d--) {
+    P.array_shape[d] = array_shape[d];
+    P.leaf_shape[d] = leaf_shape[d];
+    P.key_stride[d] = d == (int)nd - 1 ? 1 : P.key_stride[d + 1] * G.leaf_grid[d + 1];
+    P.leaf_stride[d] = d == (int)nd - 1 ? 1 : P.leaf_stride[d + 1] * leaf_shape[d + 1];
+  }
+  return ZGPU_OK;
+}
+
+int zgpu::points_mark(Scratch &sc, hipStream_t s, const void *indices, bool idx_dev, PointsFront &F) {
+  const uint64_t n = F.P.n, words = F.words;
+  const uint32_t nd = F.P.nd;
+  F.d_idx = (const uint64_t *)indices;
+  if (!idx_dev) {
+    uint64_t *d = sc.dev<uint64_t>(n * nd);
+    HIPCHK(hipMemcpyAsync(d, indices, n * nd * 8, hipMemcpyHostToDevice, s));
+    F.d_idx = d;
+  }
+  // [out-of-bounds word | bitmap], cleared and read back together
+  const uint64_t mark_words = 1 + (words + 1) / 2;
+  uint64_t *d_mark = sc.dev<uint64_t>(mark_words), *h_mark = sc.pinned<uint64_t>(mark_words);
+  F.d_bitmap = (uint32_t *)(d_mark + 1);
+  HIPCHK(hipMemsetAsync(d_mark, 0xff, 8, s));
+  HIPCHK(hipMemsetAsync(F.d_bitmap, 0, (mark_words - 1) * 8, s));
+  HIPCHK(launch_points_mark(F.d_idx, F.P, F.G.wide, F.d_bitmap, d_mark, s));
+  HIPCHK(hipMemcpyAsync(h_mark, d_mark, mark_words * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  F.bitmap = (const uint32_t *)(h_mark + 1);
+  if (h_mark[0] != UINT64_MAX) {  // IndexerError::OutOfBounds: nothing was decoded, nothing written
+    const uint64_t i = h_mark[0];
+    uint64_t p[ZG_MAXD] = {};
+    if (i < n) {
+      if (idx_dev) {
+        HIPCHK(hipMemcpyAsync(p, F.d_idx + i * nd, nd * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+      } else {
+        std::memcpy(p, (const uint64_t *)indices + i * nd, nd * 8);
+      }
+    }
+    for (uint32_t d = 0; d < nd; d++)
+      if (p[d] >= F.P.array_shape[d])
+        return set_err(ZGPU_INVALID_ARGUMENT, points_oob_message(i, d, p[d], F.P.array_shape[d]));
+    return set_err(ZGPU_INVALID_ARGUMENT, "point " + std::to_string(i) + " is out of bounds");
+  }
+  return ZGPU_OK;
+}
+
+void zgpu::points_slots(const PointsFront &F, std::vector<uint32_t> &prefix, std::vector<PointSlot> &slots,
+                        std::vector<uint64_t> &lins) {
+  prefix.assign(F.words, 0);
+  for (uint64_t w = 0; w < F.words; w++) {
+    prefix[w] = (uint32_t)slots.size();
+    for (uint32_t v = F.bitmap[w]; v; v &= v - 1) {
+      PointSlot S{};
+      points_key_chunk(F.G, w * 32 + (uint64_t)__builtin_ctz(v), &S.lin, S.origin, &S.j);
+      slots.push_back(S);
+      if (lins.empty() || lins.back() != S.lin) lins.push_back(S.lin);
+    }
+  }
+  std::sort(lins.begin(), lins.end());
+  lins.erase(std::unique(lins.begin(), lins.end()), lins.end());
+  for (PointSlot &S : slots) S.chunk = (size_t)(std::lower_bound(lins.begin(), lins.end(), S.lin) - lins.begin());
+}
 
 extern "C" int zgpu_retrieve_elements(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape,
                                       const uint64_t *chunk_shape, const void *const *chunk_ptrs,

@@ -18,6 +18,19 @@
 //   7. a shard is laid out by k_shard_layout_var / k_shard_copy_var over one item per inner chunk: the
 //      newly encoded ones, and the untouched ones pointing into the old shard; then the index crc32c.
 // Every temporary is Scratch's; the encoded chunks leave in the result (pooled pinned or device memory).
+//
+// The store by coordinates (zgpu_store_elements) is ArrayPartialEncoderTraits::partial_encode for a list of
+// ArrayIndices: CodecPartialDefault (zarrs_codec/src/codec_partial_default.rs:324-380: decode,
+// update_array_bytes, encode) with update_array_bytes_indexer (zarrs_codec/src/array_bytes.rs:685-726)
+// copying the elements in indexer order, so the last of several points on one coordinate wins. It shares
+// everything but steps 1 and 4 with the store of a box:
+//   1'. the front of the read by coordinates (points.hpp): k_points_mark, the bitmap back, a slot per
+//       touched leaf in key order; the entries are the chunks that hold a touched leaf;
+//   2, 3 as above, with EVERY touched leaf treated as partly covered and staged in its slot;
+//   4'. k_points_claim (per staged element the highest point index) and k_points_scatter (the winners
+//       write) instead of the overlay; a u32 per staged element is the winner table;
+//   5-7 as above (store_tail), nothing read straight from the data.
+// All touched leaves are staged at once: no rounds.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +45,7 @@
 #include "ctx.hpp"
 #include "kernels/launch.hpp"
 #include "plan.hpp"
+#include "points.hpp"
 #include "store_layout.hpp"
 
 using namespace zgpu;
@@ -97,91 +111,113 @@ struct Leaf {
   uint64_t slot = 0, enc_len = 0;  // encode: its slot and encoded length
 };
 
-int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const uint64_t *chunk_shape,
-                 const void *const *chunk_ptrs, const uint64_t *chunk_lens, const uint64_t *sel_start,
-                 const uint64_t *sel_shape, const void *data, uint32_t flags, const zgpu_store_entry **entries_out,
-                 uint64_t *n_out, zgpu_result **result_out, void *stream) {
-  zgpu_ctx *C = ch->ctx;
-  const Chain &top = *ch->chain;
-  const bool sharded = top.a2b.kind == CodecKind::Sharding;
-  // what the store path does not take on top of the write path's own refusals (encode_layout throws
-  // them, ChainError, before any device work): read-modify-write goes one level deep, in one data type
-  if (sharded && top.a2b.inner->a2b.kind == CodecKind::Sharding)
-    return set_err(ZGPU_UNSUPPORTED, "store: nested sharding_indexed");
-  if (sharded && chain_has_value_codec(*top.a2b.inner))
-    return set_err(ZGPU_UNSUPPORTED, "store: value codecs inside sharding_indexed");
-  const EncodeLayout EL = encode_layout(top, nd, chunk_shape);
-  const EncodeLayout &leaf_layout = sharded ? *EL.inner : EL;
-  const uint64_t *leaf_shape = sharded ? top.a2b.inner_shape.data() : chunk_shape;
-  StoreLayout L;
-  {
-    std::string err;
-    if (const int rc = store_classify(nd, array_shape, chunk_shape, leaf_shape, sel_start, sel_shape, L, err))
-      return set_err(rc, err);
-  }
-  if (L.chunks.empty()) return ZGPU_OK;
-  const bool enc_dev = flags & ZGPU_ENC_DEVICE, data_dev = flags & ZGPU_OUT_DEVICE;
-  const bool validate = ch->validate && !(flags & ZGPU_NO_VALIDATE);
-  const bool store_empty = flags & ZGPU_STORE_EMPTY_CHUNKS;
-  const uint32_t es = top.es;
-  if (data_dev && (uintptr_t)data % std::min<uint32_t>(es, 8))
-    return set_err(ZGPU_INVALID_ARGUMENT, "store: data is not aligned to its element size");
-  const uint64_t nE = L.chunks.size(), lpc = L.leaves_per_chunk, leaf_n = volume(leaf_shape, nd);
-  const uint64_t leaf_bytes = leaf_n * es;
-  std::shared_ptr<Chain> leaf_chain = sharded ? top.a2b.inner : ch->chain;
-  zgpu_chain leafch{C, leaf_chain, ch->validate};
-  const uint64_t leaf_bound = leaf_layout.size;
-  const uint64_t pitch = std::max<uint64_t>(256, align_up(leaf_bound, 256));
-  const uint64_t X = sharded ? EL.index->size : 0;
+// What a store call is made of once its chain is accepted, and its entries.
+struct StoreCall {
+  zgpu_chain *ch = nullptr;
+  zgpu_ctx *C = nullptr;
+  const Chain *top = nullptr;
+  bool sharded = false, enc_dev = false, validate = false, store_empty = false;
+  uint32_t nd = 0, es = 0, flags = 0;
+  EncodeLayout EL;
+  const EncodeLayout *leaf_layout = nullptr;
+  const uint64_t *leaf_shape = nullptr;
+  std::shared_ptr<Chain> leaf_chain;
+  uint64_t lpc = 1, leaf_n = 0, leaf_bytes = 0, leaf_bound = 0, pitch = 0, X = 0;
+  // per entry (a chunk the store meets), C order of the chunk grid
+  uint64_t nE = 0;
+  std::vector<const uint8_t *> old;  // its old bytes on the device (null: missing, or not read)
+  std::vector<uint64_t> old_len;
+  std::unique_ptr<zgpu_result> R;
+  std::vector<zgpu_store_entry> &E() { return R->store_entries; }
+};
 
-  HIPCHK(hipSetDevice(C->device));
-  uint64_t *ctr = call_counters();
-  std::fill(ctr, ctr + CTR_N, 0);
-  size_detail() = SizeDetail{};
-  std::unique_ptr<zgpu_result> R(new zgpu_result());
-  ctx_ref(C);
-  R->ctx = C;
-  std::vector<zgpu_store_entry> &E = R->store_entries;
-  E.assign(nE, zgpu_store_entry{});
-  for (uint64_t k = 0; k < nE; k++) E[k].chunk = L.chunks[k].lin;
-
-  // host tables the queued copies read: declared before the scratch, whose destructor waits for them
-  std::vector<uint64_t> index(sharded ? nE * lpc * 2 : 0, ~0ull), rows, starts, hsh;
+// Host tables the queued copies read: declared before the scratch, whose destructor waits for them.
+struct StoreTables {
+  std::vector<uint64_t> index, rows, starts, hsh, dst;
+  std::vector<uint32_t> nf, prefix;
   std::vector<Leaf> leaves;
   std::vector<zgpu_chunk_desc> descs;
   std::vector<ZgOverlayBox> boxes;
   std::vector<ZgItem> items;
-  std::vector<uint32_t> nf;
-  LaneScope ls(C);
-  hipStream_t s = pick_stream(ls.L, stream);
-  Scratch sc(C, s);
+  std::vector<PointSlot> slots;
+};
 
-  // the data and the old chunks the subset does not cover, on the device
-  const uint64_t data_bytes = volume(sel_shape, nd) * es;
-  const uint8_t *d_data = (const uint8_t *)data;
-  if (!data_dev) {
-    uint8_t *d = sc.dev<uint8_t>(data_bytes);
-    HIPCHK(hipMemcpyAsync(d, data, data_bytes, hipMemcpyHostToDevice, s));
-    d_data = d;
-  }
-  std::vector<const uint8_t *> old(nE, nullptr);
-  std::vector<uint64_t> old_len(nE, 0);
+// The chain's refusals (ZGPU_UNSUPPORTED, or ChainError thrown by encode_layout: before any device work)
+// and the leaf's layout.
+int store_accept(zgpu_chain *ch, uint32_t nd, const uint64_t *chunk_shape, uint32_t flags, StoreCall &S) {
+  S.ch = ch;
+  S.C = ch->ctx;
+  S.top = ch->chain.get();
+  const Chain &top = *S.top;
+  S.sharded = top.a2b.kind == CodecKind::Sharding;
+  // what the store path does not take on top of the write path's own refusals (encode_layout throws
+  // them, ChainError, before any device work): read-modify-write goes one level deep, in one data type
+  if (S.sharded && top.a2b.inner->a2b.kind == CodecKind::Sharding)
+    return set_err(ZGPU_UNSUPPORTED, "store: nested sharding_indexed");
+  if (S.sharded && chain_has_value_codec(*top.a2b.inner))
+    return set_err(ZGPU_UNSUPPORTED, "store: value codecs inside sharding_indexed");
+  S.EL = encode_layout(top, nd, chunk_shape);
+  S.leaf_layout = S.sharded ? S.EL.inner.get() : &S.EL;
+  S.leaf_shape = S.sharded ? top.a2b.inner_shape.data() : chunk_shape;
+  S.nd = nd;
+  S.es = top.es;
+  S.flags = flags;
+  S.enc_dev = flags & ZGPU_ENC_DEVICE;
+  S.validate = ch->validate && !(flags & ZGPU_NO_VALIDATE);
+  S.store_empty = flags & ZGPU_STORE_EMPTY_CHUNKS;
+  S.lpc = 1;
+  for (uint32_t d = 0; d < nd; d++) S.lpc *= chunk_shape[d] / S.leaf_shape[d];
+  S.leaf_n = volume(S.leaf_shape, nd);
+  S.leaf_bytes = S.leaf_n * S.es;
+  S.leaf_chain = S.sharded ? top.a2b.inner : ch->chain;
+  S.leaf_bound = S.leaf_layout->size;
+  S.pitch = std::max<uint64_t>(256, align_up(S.leaf_bound, 256));
+  S.X = S.sharded ? S.EL.index->size : 0;
+  return ZGPU_OK;
+}
+
+// The call's device, its counters cleared, its result with one entry per chunk of lins.
+void store_begin(StoreCall &S, const uint64_t *lins, uint64_t nE) {
+  HIPCHK(hipSetDevice(S.C->device));
+  uint64_t *ctr = call_counters();
+  std::fill(ctr, ctr + CTR_N, 0);
+  size_detail() = SizeDetail{};
+  S.R.reset(new zgpu_result());
+  ctx_ref(S.C);
+  S.R->ctx = S.C;
+  S.nE = nE;
+  S.E().assign(nE, zgpu_store_entry{});
+  for (uint64_t k = 0; k < nE; k++) S.E()[k].chunk = lins[k];
+  S.old.assign(nE, nullptr);
+  S.old_len.assign(nE, 0);
+}
+
+// The old chunks of the entries with need[k] whose key is present, on the device; the old shards' indexes
+// decoded and range-checked on the host into T.index (a failure is the entry's status).
+void store_old_chunks(StoreCall &S, StoreTables &T, Scratch &sc, hipStream_t s, const void *const *chunk_ptrs,
+                      const uint64_t *chunk_lens, const std::vector<uint8_t> &need) {
+  const uint64_t nE = S.nE, X = S.X, lpc = S.lpc;
+  const Chain &top = *S.top;
+  std::vector<zgpu_store_entry> &E = S.E();
+  std::vector<const uint8_t *> &old = S.old;
+  std::vector<uint64_t> &old_len = S.old_len;
+  T.index.assign(S.sharded ? nE * lpc * 2 : 0, ~0ull);
   {
     constexpr uint64_t HR = 64;  // readable bytes either side of an old chunk (launch_unpackbits)
     uint64_t total = 0;
     std::vector<uint64_t> off(nE, 0);
     for (uint64_t k = 0; k < nE; k++) {
-      const uint64_t lin = L.chunks[k].lin;
-      if (L.chunks[k].covered || !chunk_ptrs[lin]) continue;
+      const uint64_t lin = E[k].chunk;
+      if (!need[k] || !chunk_ptrs[lin]) continue;
       old_len[k] = chunk_lens[lin];
       off[k] = total + HR;
       total += align_up(HR + old_len[k] + HR, 256);
     }
-    uint8_t *pack = (!enc_dev && total) ? sc.dev<uint8_t>(total) : nullptr;
+    uint8_t *pack = (!S.enc_dev && total) ? sc.dev<uint8_t>(total) : nullptr;
     for (uint64_t k = 0; k < nE; k++) {
-      const uint64_t lin = L.chunks[k].lin;
-      if (L.chunks[k].covered || !chunk_ptrs[lin]) continue;
-      if (enc_dev) {
+      const uint64_t lin = E[k].chunk;
+      if (!need[k] || !chunk_ptrs[lin]) continue;
+      if (S.enc_dev) {
         old[k] = (const uint8_t *)chunk_ptrs[lin];
       } else {
         old[k] = pack + off[k];
@@ -191,10 +227,10 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
   }
 
   // the old shards' indexes, decoded and range-checked on the host
-  if (sharded) {
+  if (S.sharded) {
     const Chain &xc = *top.a2b.index;
     uint8_t *hx = nullptr;
-    if (enc_dev) {
+    if (S.enc_dev) {
       hx = sc.pinned<uint8_t>(std::max<uint64_t>(nE * X, 1));
       for (uint64_t k = 0; k < nE; k++)
         if (old[k] && old_len[k] >= X)
@@ -207,107 +243,89 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
         E[k].status = ZGPU_SHARD_TOO_SMALL;
         continue;
       }
-      const uint8_t *src = enc_dev ? hx + k * X
-                                   : (const uint8_t *)chunk_ptrs[L.chunks[k].lin] + (top.a2b.at_start ? 0 : old_len[k] - X);
-      E[k].status = parse_index(src, X, xc, lpc, validate, old_len[k], index.data() + k * lpc * 2);
+      const uint8_t *src = S.enc_dev ? hx + k * X
+                                     : (const uint8_t *)chunk_ptrs[E[k].chunk] + (top.a2b.at_start ? 0 : old_len[k] - X);
+      E[k].status = parse_index(src, X, xc, lpc, S.validate, old_len[k], T.index.data() + k * lpc * 2);
     }
   }
+}
 
-  // the leaves the subset touches
-  uint64_t n_stage = 0;
-  for (uint64_t k = 0; k < nE; k++) {
-    if (E[k].status) continue;
-    for (uint64_t j = 0; j < lpc; j++) {
-      const uint8_t cls = L.leaf_class[L.chunks[k].first_leaf + j];
-      if (cls == ZGPU_LEAF_UNTOUCHED) continue;
-      Leaf lf{};
-      lf.entry = k;
-      lf.j = j;
-      store_leaf_origin(L, L.chunks[k], leaf_shape, j, lf.origin);
-      lf.partial = cls == ZGPU_LEAF_PARTIAL;
-      if (lf.partial) {
-        lf.stage = n_stage++;
-        if (!sharded) {
-          lf.old = old[k];
-          lf.old_len = old_len[k];
-        } else if (old[k] && index[(k * lpc + j) * 2] != ~0ull) {
-          lf.old = old[k] + index[(k * lpc + j) * 2];
-          lf.old_len = index[(k * lpc + j) * 2 + 1];
-        }
-      }
-      leaves.push_back(lf);
-    }
+// A staged leaf's old encoded bytes: the chunk's, or the inner chunk's as the old shard's index gives them.
+void leaf_old_bytes(const StoreCall &S, const StoreTables &T, Leaf &lf) {
+  const uint64_t k = lf.entry, q = (k * S.lpc + lf.j) * 2;
+  if (!S.sharded) {
+    lf.old = S.old[k];
+    lf.old_len = S.old_len[k];
+  } else if (S.old[k] && T.index[q] != ~0ull) {
+    lf.old = S.old[k] + T.index[q];
+    lf.old_len = T.index[q + 1];
   }
+}
 
-  // one decode batch of the partly covered leaves into the staging array, one overlay launch
-  uint64_t stage_shape[ZG_MAXD], stage_stride[ZG_MAXD], sel_stride[ZG_MAXD];
-  for (uint32_t d = 0; d < nd; d++) stage_shape[d] = leaf_shape[d];
-  stage_shape[0] = std::max<uint64_t>(n_stage, 1) * leaf_shape[0];
-  for (int d = (int)nd - 1; d >= 0; d--) {
-    stage_stride[d] = d == (int)nd - 1 ? 1 : stage_stride[d + 1] * stage_shape[d + 1];
-    sel_stride[d] = d == (int)nd - 1 ? 1 : sel_stride[d + 1] * sel_shape[d + 1];
+// Step 3: one decode batch of the staged leaves (T.leaves with partial set) into the staging array; a
+// failing leaf gives its entry its status. Synchronises s.
+void store_decode_staged(StoreCall &S, StoreTables &T, hipStream_t s, uint8_t *staging, const uint64_t *stage_shape) {
+  uint64_t *ctr = call_counters();
+  std::vector<zgpu_store_entry> &E = S.E();
+  std::vector<uint64_t> owner;
+  for (const Leaf &lf : T.leaves) {
+    if (!lf.partial) continue;
+    zgpu_chunk_desc D{};
+    D.enc = lf.old;
+    D.enc_len = lf.old ? lf.old_len : 0;
+    for (uint32_t d = 0; d < S.nd; d++) {
+      D.chunk_shape[d] = D.sel_shape[d] = S.leaf_shape[d];
+      D.out_start[d] = d == 0 ? lf.stage * S.leaf_shape[0] : 0;
+    }
+    T.descs.push_back(D);
+    owner.push_back(lf.entry);
+    if (lf.old) ctr[CTR_STORE_DECODED]++;
   }
-  uint8_t *staging = n_stage ? sc.dev<uint8_t>(n_stage * leaf_bytes) : nullptr;
-  if (n_stage) {
-    std::vector<uint64_t> owner;
-    for (const Leaf &lf : leaves) {
-      if (!lf.partial) continue;
-      zgpu_chunk_desc D{};
-      D.enc = lf.old;
-      D.enc_len = lf.old ? lf.old_len : 0;
-      for (uint32_t d = 0; d < nd; d++) {
-        D.chunk_shape[d] = D.sel_shape[d] = leaf_shape[d];
-        D.out_start[d] = d == 0 ? lf.stage * leaf_shape[0] : 0;
-      }
-      descs.push_back(D);
-      owner.push_back(lf.entry);
-      if (lf.old) ctr[CTR_STORE_DECODED]++;
-    }
-    GeneralCall G{C, validate, nd, staging, stage_shape, (flags & ZGPU_NO_VALIDATE) | ZGPU_ENC_DEVICE | ZGPU_OUT_DEVICE,
-                  s, {}};
-    std::vector<int32_t> st(descs.size(), 0);
-    decode_general(G, leaf_chain, descs.data(), descs.size(), st.data());
-    HIPCHK(hipStreamSynchronize(s));
-    for (size_t i = 0; i < st.size(); i++)
-      if (st[i] && !E[owner[i]].status) E[owner[i]].status = st[i];
-    // the overlap of every staged leaf of a chunk still in good standing
-    rows.push_back(0);
-    for (const Leaf &lf : leaves) {
-      if (!lf.partial || E[lf.entry].status) continue;
-      ZgOverlayBox B{};
-      uint64_t so = 0, dof = lf.stage * leaf_shape[0] * stage_stride[0], nr = 1;
-      for (uint32_t d = 0; d < nd; d++) {
-        const uint64_t lo = std::max(lf.origin[d], sel_start[d]);
-        const uint64_t hi = std::min(lf.origin[d] + leaf_shape[d], sel_start[d] + sel_shape[d]);
-        B.ext[d] = hi - lo;
-        B.src_stride[d] = sel_stride[d];
-        B.dst_stride[d] = stage_stride[d];
-        so += (lo - sel_start[d]) * sel_stride[d];
-        dof += (lo - lf.origin[d]) * stage_stride[d];
-        if (d + 1 < nd) nr *= B.ext[d];
-      }
-      B.src = (uint64_t)(d_data + so * es);
-      B.dst = (uint64_t)(staging + dof * es);
-      boxes.push_back(B);
-      rows.push_back(rows.back() + nr);
-    }
-    if (!boxes.empty()) {
-      ZgOverlayBox *d_boxes = sc.dev<ZgOverlayBox>(boxes.size());
-      uint64_t *d_rows = sc.dev<uint64_t>(rows.size());
-      HIPCHK(hipMemcpyAsync(d_boxes, boxes.data(), boxes.size() * sizeof(ZgOverlayBox), hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, s));
-      HIPCHK(launch_subset_overlay(d_boxes, d_rows, (uint32_t)boxes.size(), rows.back(), nd, es, s));
-    }
-  }
+  GeneralCall G{S.C, S.validate, S.nd, staging, stage_shape,
+                (S.flags & ZGPU_NO_VALIDATE) | ZGPU_ENC_DEVICE | ZGPU_OUT_DEVICE, s, {}};
+  std::vector<int32_t> st(T.descs.size(), 0);
+  decode_general(G, S.leaf_chain, T.descs.data(), T.descs.size(), st.data());
+  HIPCHK(hipStreamSynchronize(s));
+  for (size_t i = 0; i < st.size(); i++)
+    if (st[i] && !E[owner[i]].status) E[owner[i]].status = st[i];
+}
+
+// Where the covered leaves are read from (the store of a box): the data, the subset's box and strides.
+struct StoreData {
+  const uint8_t *d_data = nullptr;
+  const uint64_t *sel_start = nullptr, *sel_shape = nullptr, *sel_stride = nullptr;
+};
+
+// Steps 5-7 over the leaves of the entries still in good standing: the fill check, the encode of what is
+// not all fill, every entry's action, the shard layout, the copy-out; the result is handed over.
+int store_tail(StoreCall &S, StoreTables &T, Scratch &sc, hipStream_t s, uint8_t *staging, const uint64_t *stage_shape,
+               const uint64_t *stage_stride, const StoreData &SD, const zgpu_store_entry **entries_out, uint64_t *n_out,
+               zgpu_result **result_out) {
+  zgpu_ctx *C = S.C;
+  const Chain &top = *S.top;
+  const EncodeLayout &EL = S.EL;
+  const bool sharded = S.sharded, enc_dev = S.enc_dev, store_empty = S.store_empty;
+  const uint32_t nd = S.nd, es = S.es;
+  const uint64_t nE = S.nE, lpc = S.lpc, leaf_n = S.leaf_n, leaf_bound = S.leaf_bound, pitch = S.pitch, X = S.X;
+  const uint64_t *leaf_shape = S.leaf_shape;
+  zgpu_chain leafch{C, S.leaf_chain, S.ch->validate};
+  std::unique_ptr<zgpu_result> &R = S.R;
+  std::vector<zgpu_store_entry> &E = S.E();
+  std::vector<const uint8_t *> &old = S.old;
+  std::vector<uint64_t> &index = T.index, &starts = T.starts, &hsh = T.hsh;
+  std::vector<Leaf> &leaves = T.leaves;
+  std::vector<ZgItem> &items = T.items;
+  std::vector<uint32_t> &nf = T.nf;
+  uint64_t *ctr = call_counters();
 
   // the leaves to go on with, staged ones first; their origins in the array each group reads
   std::vector<Leaf *> group[2];  // [0] staged (array: the staging array), [1] covered (array: the data)
   for (Leaf &lf : leaves)
     if (!E[lf.entry].status) group[lf.partial ? 0 : 1].push_back(&lf);
-  const void *g_array[2] = {staging, d_data};
-  const uint64_t *g_shape[2] = {stage_shape, sel_shape};
+  const void *g_array[2] = {staging, SD.d_data};
+  const uint64_t *g_shape[2] = {stage_shape, SD.sel_shape};
   auto leaf_start = [&](const Leaf &lf, uint32_t d) {
-    return lf.partial ? (d == 0 ? lf.stage * leaf_shape[0] : 0) : lf.origin[d] - sel_start[d];
+    return lf.partial ? (d == 0 ? lf.stage * leaf_shape[0] : 0) : lf.origin[d] - SD.sel_start[d];
   };
 
   // rule 3: which leaves equal the fill value everywhere (bytewise, k_fill_check)
@@ -324,6 +342,7 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
     HIPCHK(hipMemcpyAsync(d_starts, starts.data(), starts.size() * 8, hipMemcpyHostToDevice, s));
     uint64_t base = 0;
     for (int g = 0; g < 2; g++) {
+      if (group[g].empty()) continue;
       ZgEncode P{};
       P.nd = nd;
       P.es = es;
@@ -332,11 +351,10 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
       for (uint32_t d = 0; d < nd; d++) {
         P.dec_shape[d] = leaf_shape[d];
         P.array_shape[d] = g_shape[g][d];
-        P.array_stride[d] = g == 0 ? stage_stride[d] : sel_stride[d];
+        P.array_stride[d] = g == 0 ? stage_stride[d] : SD.sel_stride[d];
       }
-      if (!group[g].empty())
-        HIPCHK(launch_fill_check(d_starts + base * nd, (const uint8_t *)g_array[g], P, (uint32_t)group[g].size(),
-                                 d_nf + base, s));
+      HIPCHK(launch_fill_check(d_starts + base * nd, (const uint8_t *)g_array[g], P, (uint32_t)group[g].size(),
+                               d_nf + base, s));
       base += group[g].size();
     }
     if (n_all) HIPCHK(hipMemcpyAsync(h_nf, d_nf, n_all * 4, hipMemcpyDeviceToHost, s));
@@ -441,16 +459,16 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
       for (uint64_t i = 0; i < nS; i++) hsh[i] = (uint64_t)(out_dev + e_off[set[i]]);
       ZgItem *d_items = sc.dev<ZgItem>(items.size());
       // (A.E_pitch: the largest shard; the item and shard statuses behind the fill flags)
-      const ShardTables T = shard_tables(sc, EL, hsh.data(), nS, items.size(), nf.size() + items.size() + nS, 0, cap, s);
-      uint32_t *d_ist = T.nf + nf.size(), *d_shst = d_ist + items.size();
+      const ShardTables ST = shard_tables(sc, EL, hsh.data(), nS, items.size(), nf.size() + items.size() + nS, 0, cap, s);
+      uint32_t *d_ist = ST.nf + nf.size(), *d_shst = d_ist + items.size();
       HIPCHK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(ZgItem), hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(T.nf, nf.data(), nf.size() * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(ST.nf, nf.data(), nf.size() * 4, hipMemcpyHostToDevice, s));
       HIPCHK(hipMemsetAsync(d_ist, 0, (items.size() + nS) * 4, s));
-      HIPCHK(launch_shard_layout_var((uint32_t)items.size(), T.nf, d_items, d_ist, T.A, T.dst, T.off, T.index_ptr, T.len,
+      HIPCHK(launch_shard_layout_var((uint32_t)items.size(), ST.nf, d_items, d_ist, ST.A, ST.dst, ST.off, ST.index_ptr, ST.len,
                                      d_shst, (uint32_t)nS, s));
-      checksums_in_place(T.index_ptr, (uint32_t)nS, *EL.index, s);
+      checksums_in_place(ST.index_ptr, (uint32_t)nS, *EL.index, s);
       uint64_t *h_len = sc.pinned<uint64_t>(2 * nS);
-      HIPCHK(hipMemcpyAsync(h_len, T.len, nS * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(h_len, ST.len, nS * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(hipMemcpyAsync(h_len + nS, d_shst, nS * 4, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       for (uint64_t i = 0; i < nS; i++)
@@ -489,6 +507,218 @@ int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const
   return rc;
 }
 
+int store_subset(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const uint64_t *chunk_shape,
+                 const void *const *chunk_ptrs, const uint64_t *chunk_lens, const uint64_t *sel_start,
+                 const uint64_t *sel_shape, const void *data, uint32_t flags, const zgpu_store_entry **entries_out,
+                 uint64_t *n_out, zgpu_result **result_out, void *stream) {
+  StoreCall S;
+  if (const int rc = store_accept(ch, nd, chunk_shape, flags, S)) return rc;
+  const uint64_t *leaf_shape = S.leaf_shape;
+  StoreLayout L;
+  {
+    std::string err;
+    if (const int rc = store_classify(nd, array_shape, chunk_shape, leaf_shape, sel_start, sel_shape, L, err))
+      return set_err(rc, err);
+  }
+  if (L.chunks.empty()) return ZGPU_OK;
+  const bool data_dev = flags & ZGPU_OUT_DEVICE;
+  const uint32_t es = S.es;
+  if (data_dev && (uintptr_t)data % std::min<uint32_t>(es, 8))
+    return set_err(ZGPU_INVALID_ARGUMENT, "store: data is not aligned to its element size");
+  const uint64_t nE = L.chunks.size(), lpc = L.leaves_per_chunk;
+  {
+    std::vector<uint64_t> lins(nE);
+    for (uint64_t k = 0; k < nE; k++) lins[k] = L.chunks[k].lin;
+    store_begin(S, lins.data(), nE);
+  }
+  std::vector<zgpu_store_entry> &E = S.E();
+
+  StoreTables T;
+  std::vector<Leaf> &leaves = T.leaves;
+  LaneScope ls(S.C);
+  hipStream_t s = pick_stream(ls.L, stream);
+  Scratch sc(S.C, s);
+
+  // the data and the old chunks the subset does not cover, on the device
+  const uint64_t data_bytes = volume(sel_shape, nd) * es;
+  const uint8_t *d_data = (const uint8_t *)data;
+  if (!data_dev) {
+    uint8_t *d = sc.dev<uint8_t>(data_bytes);
+    HIPCHK(hipMemcpyAsync(d, data, data_bytes, hipMemcpyHostToDevice, s));
+    d_data = d;
+  }
+  {
+    std::vector<uint8_t> need(nE);
+    for (uint64_t k = 0; k < nE; k++) need[k] = !L.chunks[k].covered;
+    store_old_chunks(S, T, sc, s, chunk_ptrs, chunk_lens, need);
+  }
+
+  // the leaves the subset touches
+  uint64_t n_stage = 0;
+  for (uint64_t k = 0; k < nE; k++) {
+    if (E[k].status) continue;
+    for (uint64_t j = 0; j < lpc; j++) {
+      const uint8_t cls = L.leaf_class[L.chunks[k].first_leaf + j];
+      if (cls == ZGPU_LEAF_UNTOUCHED) continue;
+      Leaf lf{};
+      lf.entry = k;
+      lf.j = j;
+      store_leaf_origin(L, L.chunks[k], leaf_shape, j, lf.origin);
+      lf.partial = cls == ZGPU_LEAF_PARTIAL;
+      if (lf.partial) {
+        lf.stage = n_stage++;
+        leaf_old_bytes(S, T, lf);
+      }
+      leaves.push_back(lf);
+    }
+  }
+
+  // one decode batch of the partly covered leaves into the staging array, one overlay launch
+  uint64_t stage_shape[ZG_MAXD], stage_stride[ZG_MAXD], sel_stride[ZG_MAXD];
+  for (uint32_t d = 0; d < nd; d++) stage_shape[d] = leaf_shape[d];
+  stage_shape[0] = std::max<uint64_t>(n_stage, 1) * leaf_shape[0];
+  for (int d = (int)nd - 1; d >= 0; d--) {
+    stage_stride[d] = d == (int)nd - 1 ? 1 : stage_stride[d + 1] * stage_shape[d + 1];
+    sel_stride[d] = d == (int)nd - 1 ? 1 : sel_stride[d + 1] * sel_shape[d + 1];
+  }
+  uint8_t *staging = n_stage ? sc.dev<uint8_t>(n_stage * S.leaf_bytes) : nullptr;
+  if (n_stage) {
+    store_decode_staged(S, T, s, staging, stage_shape);
+    // the overlap of every staged leaf of a chunk still in good standing
+    std::vector<uint64_t> &rows = T.rows;
+    std::vector<ZgOverlayBox> &boxes = T.boxes;
+    rows.push_back(0);
+    for (const Leaf &lf : leaves) {
+      if (!lf.partial || E[lf.entry].status) continue;
+      ZgOverlayBox B{};
+      uint64_t so = 0, dof = lf.stage * leaf_shape[0] * stage_stride[0], nr = 1;
+      for (uint32_t d = 0; d < nd; d++) {
+        const uint64_t lo = std::max(lf.origin[d], sel_start[d]);
+        const uint64_t hi = std::min(lf.origin[d] + leaf_shape[d], sel_start[d] + sel_shape[d]);
+        B.ext[d] = hi - lo;
+        B.src_stride[d] = sel_stride[d];
+        B.dst_stride[d] = stage_stride[d];
+        so += (lo - sel_start[d]) * sel_stride[d];
+        dof += (lo - lf.origin[d]) * stage_stride[d];
+        if (d + 1 < nd) nr *= B.ext[d];
+      }
+      B.src = (uint64_t)(d_data + so * es);
+      B.dst = (uint64_t)(staging + dof * es);
+      boxes.push_back(B);
+      rows.push_back(rows.back() + nr);
+    }
+    if (!boxes.empty()) {
+      ZgOverlayBox *d_boxes = sc.dev<ZgOverlayBox>(boxes.size());
+      uint64_t *d_rows = sc.dev<uint64_t>(rows.size());
+      HIPCHK(hipMemcpyAsync(d_boxes, boxes.data(), boxes.size() * sizeof(ZgOverlayBox), hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(d_rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice, s));
+      HIPCHK(launch_subset_overlay(d_boxes, d_rows, (uint32_t)boxes.size(), rows.back(), nd, es, s));
+    }
+  }
+  const StoreData SD{d_data, sel_start, sel_shape, sel_stride};
+  return store_tail(S, T, sc, s, staging, stage_shape, stage_stride, SD, entries_out, n_out, result_out);
+}
+
+// zgpu_store_elements: see the header of this file and zgpu.h.
+int store_points(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const uint64_t *chunk_shape,
+                 const void *const *chunk_ptrs, const uint64_t *chunk_lens, const void *indices, uint64_t n,
+                 const void *data, uint32_t flags, const zgpu_store_entry **entries_out, uint64_t *n_out,
+                 zgpu_result **result_out, void *stream) {
+  uint64_t *ctr = call_counters();
+  std::fill(ctr, ctr + CTR_N, 0);  // (a refused call reports no work of an earlier one)
+  StoreCall S;
+  if (const int rc = store_accept(ch, nd, chunk_shape, flags, S)) return rc;
+  const uint32_t es = S.es;
+  if (es != 1 && es != 2 && es != 4 && es != 8 && es != 16)
+    return set_err(ZGPU_UNSUPPORTED, "store_elements: element size " + std::to_string(es));
+  if (n >= UINT32_MAX)
+    return set_err(ZGPU_UNSUPPORTED, "store_elements: " + std::to_string(n) + " points; the winner table holds a "
+                                     "point's index + 1 in 32 bits, so a call takes fewer than 2^32 - 1 points");
+  const uint64_t *leaf_shape = S.leaf_shape;
+  PointsFront F;
+  if (const int rc = points_plan("store_elements", nd, array_shape, chunk_shape, leaf_shape, S.top->fill, indices, n, F))
+    return rc;
+  const bool data_dev = flags & ZGPU_OUT_DEVICE, idx_dev = flags & ZGPU_IDX_DEVICE;
+  if (n && data_dev && (uintptr_t)data % std::min<uint32_t>(es, 8))
+    return set_err(ZGPU_INVALID_ARGUMENT, "store_elements: data is not aligned to its element size");
+  HIPCHK(hipSetDevice(S.C->device));
+  size_detail() = SizeDetail{};
+  if (!n) return ZGPU_OK;
+
+  StoreTables T;
+  std::vector<uint64_t> lins;
+  LaneScope ls(S.C);
+  hipStream_t s = pick_stream(ls.L, stream);
+  Scratch sc(S.C, s);
+
+  // 1'. the data on the device; mark, the bitmap back; a slot per touched leaf, the chunks that hold one
+  const uint8_t *d_data = (const uint8_t *)data;
+  if (!data_dev) {
+    uint8_t *d = sc.dev<uint8_t>(n * es);
+    HIPCHK(hipMemcpyAsync(d, data, n * es, hipMemcpyHostToDevice, s));
+    d_data = d;
+  }
+  if (const int rc = points_mark(sc, s, indices, idx_dev, F)) return rc;
+  points_slots(F, T.prefix, T.slots, lins);
+  const uint64_t n_slots = T.slots.size(), nE = lins.size();
+  store_begin(S, lins.data(), nE);
+  ctr[CTR_POINT_LEAVES] = n_slots;
+  std::vector<zgpu_store_entry> &E = S.E();
+
+  // 2. only the chunks the points touch are read
+  store_old_chunks(S, T, sc, s, chunk_ptrs, chunk_lens, std::vector<uint8_t>(nE, 1));
+
+  // every touched leaf is partly covered and staged in its slot (a failed entry's slots stay unused)
+  for (uint64_t i = 0; i < n_slots; i++) {
+    const PointSlot &PS = T.slots[i];
+    if (E[PS.chunk].status) continue;
+    Leaf lf{};
+    lf.entry = PS.chunk;
+    lf.j = PS.j;
+    uint64_t rem = PS.lin;
+    for (int d = (int)nd - 1; d >= 0; d--) {
+      lf.origin[d] = rem % F.G.chunk_grid[d] * chunk_shape[d] + PS.origin[d];
+      rem /= F.G.chunk_grid[d];
+    }
+    lf.partial = true;
+    lf.stage = i;
+    leaf_old_bytes(S, T, lf);
+    T.leaves.push_back(lf);
+  }
+  uint64_t stage_shape[ZG_MAXD], stage_stride[ZG_MAXD];
+  for (uint32_t d = 0; d < nd; d++) stage_shape[d] = leaf_shape[d];
+  stage_shape[0] = n_slots * leaf_shape[0];
+  for (int d = (int)nd - 1; d >= 0; d--) stage_stride[d] = d == (int)nd - 1 ? 1 : stage_stride[d + 1] * stage_shape[d + 1];
+  const uint64_t stage_bytes = n_slots * S.leaf_bytes, winner_bytes = n_slots * S.leaf_n * 4;
+  uint8_t *staging = nullptr;
+  uint32_t *winner = nullptr;
+  try {
+    staging = sc.dev<uint8_t>(stage_bytes);
+    winner = sc.dev<uint32_t>(n_slots * S.leaf_n);
+  } catch (const HipFail &e) {
+    return set_err(ZGPU_HIP_ERROR, "store_elements: no memory for " + std::to_string(stage_bytes) +
+                                       " staged bytes (all touched leaves at once: no rounds) and " +
+                                       std::to_string(winner_bytes) + " bytes of winner table: " + hipGetErrorString(e.e));
+  }
+  HIPCHK(hipMemsetAsync(winner, 0, winner_bytes, s));
+
+  // 3. one decode batch of the touched leaves
+  if (!T.leaves.empty()) store_decode_staged(S, T, s, staging, stage_shape);
+
+  // 4'. claim, then scatter: per slot the staged leaf, or SKIP for an entry that failed
+  T.dst.assign(n_slots, ZG_POINTS_SKIP);
+  for (uint64_t i = 0; i < n_slots; i++)
+    if (!E[T.slots[i].chunk].status) T.dst[i] = (uint64_t)(staging + i * S.leaf_bytes);
+  uint64_t *d_dst = sc.dev<uint64_t>(n_slots);
+  uint32_t *d_prefix = sc.dev<uint32_t>(F.words);
+  HIPCHK(hipMemcpyAsync(d_dst, T.dst.data(), n_slots * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(d_prefix, T.prefix.data(), F.words * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(launch_points_claim(F.d_idx, F.P, F.G.wide, S.leaf_n, F.d_bitmap, d_prefix, d_dst, winner, s));
+  HIPCHK(launch_points_scatter(F.d_idx, F.P, F.G.wide, es, S.leaf_n, F.d_bitmap, d_prefix, d_dst, winner, d_data, s));
+
+  return store_tail(S, T, sc, s, staging, stage_shape, stage_stride, StoreData{}, entries_out, n_out, result_out);
+}
+
 }  // namespace
 
 extern "C" int zgpu_store_entry_copy(zgpu_chain *ch, const zgpu_store_entry *e, void *dst, void *stream) {
@@ -520,5 +750,22 @@ extern "C" int zgpu_store_array_subset(zgpu_chain *ch, uint32_t nd, const uint64
   if (!data && volume(sel_shape, nd)) return set_err(ZGPU_INVALID_ARGUMENT, "NULL argument");
   return store_subset(ch, nd, array_shape, chunk_shape, chunk_ptrs, chunk_lens, sel_start, sel_shape, data, flags,
                       entries, n_entries, result, stream);
+  ABI_GUARD_END
+}
+
+extern "C" int zgpu_store_elements(zgpu_chain *ch, uint32_t nd, const uint64_t *array_shape, const uint64_t *chunk_shape,
+                                   const void *const *chunk_ptrs, const uint64_t *chunk_lens, const void *indices,
+                                   uint64_t n, const void *data, uint32_t flags, const zgpu_store_entry **entries,
+                                   uint64_t *n_entries, zgpu_result **result, void *stream) {
+  ABI_GUARD_BEGIN
+  if (entries) *entries = nullptr;
+  if (n_entries) *n_entries = 0;
+  if (result) *result = nullptr;
+  if (!ch || !array_shape || !chunk_shape || !chunk_ptrs || !chunk_lens || !entries || !n_entries || !result ||
+      (n && (!indices || !data)))
+    return set_err(ZGPU_INVALID_ARGUMENT, "NULL argument");
+  if (nd == 0 || nd > ZGPU_MAX_DIMS) return set_err(ZGPU_INVALID_ARGUMENT, "ndim out of range");
+  return store_points(ch, nd, array_shape, chunk_shape, chunk_ptrs, chunk_lens, indices, n, data, flags, entries,
+                      n_entries, result, stream);
   ABI_GUARD_END
 }
