@@ -382,7 +382,10 @@ void zgpu_group_destroy(zgpu_group *group);
                                     points touch: staged, read from the cache, or read as the fill value    */
 #define ZGPU_CTR_POINT_ROUNDS 13 /* zgpu_retrieve_elements: decode + gather rounds: 1 when the touched leaves fit
                                     ZGPU_POINTS_SCRATCH_MB (and for the cache), more when they are cut     */
-#define ZGPU_N_COUNTERS 14
+#define ZGPU_CTR_BLOSC_ALIASED 14 /* zstd blocks inside blosc frames that k_blosc_finish read where they lay
+                                    (raw, RLE or literal-only blocks left out of the stream's slot: at most
+                                    two per stream; 0 with ZGPU_BLOSC_ALIAS=0 and for serially decoded streams) */
+#define ZGPU_N_COUNTERS 15
 uint32_t zgpu_plan_counters(const zgpu_plan *plan, uint64_t *out, uint32_t n);
 uint32_t zgpu_last_counters(uint64_t *out, uint32_t n);
 

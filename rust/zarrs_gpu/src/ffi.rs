@@ -75,7 +75,9 @@ pub const ZGPU_CTR_STORE_CARRIED: usize = 11;
 /// zgpu_retrieve_elements: distinct leaves the points touch; decode + gather rounds.
 pub const ZGPU_CTR_POINT_LEAVES: usize = 12;
 pub const ZGPU_CTR_POINT_ROUNDS: usize = 13;
-pub const ZGPU_N_COUNTERS: usize = 14;
+/// zstd blocks inside blosc frames read where they lay (block aliases).
+pub const ZGPU_CTR_BLOSC_ALIASED: usize = 14;
+pub const ZGPU_N_COUNTERS: usize = 15;
 
 /// zgpu_store_entry.action
 pub const ZGPU_STORE_SET: u32 = 1;

@@ -145,6 +145,8 @@ class Call:
         ctr = (C.c_uint64 * L.N_COUNTERS)()
         if self.plan is not None:
             L.load().zgpu_plan_counters(self.plan, ctr, L.N_COUNTERS)
+        else:  # host input: the calling thread's last call
+            L.load().zgpu_last_counters(ctr, L.N_COUNTERS)
         return list(ctr)
 
     def close(self):

@@ -52,8 +52,8 @@ EXPORTS = [
 SCATTER_ROWS, SCATTER_TILED, SCATTER_GENERIC, SCATTER_TILED_PERSISTENT = range(4)  # zgpu_plan_scatter_path
 CTR_ENC_BYTES, CTR_ZSTD_SERIAL, CTR_ZSTD_PARALLEL, CTR_BLOSC_RERUN, CTR_BLOSC_BLOCKS, CTR_ITEMS, \
     CTR_ZSTD_LATENCY, CTR_BZ2_BLOCKS, CTR_BZ2_ROUNDS, CTR_STORE_DECODED, CTR_STORE_ENCODED, \
-    CTR_STORE_CARRIED, CTR_POINT_LEAVES, CTR_POINT_ROUNDS = range(14)
-N_COUNTERS = 14
+    CTR_STORE_CARRIED, CTR_POINT_LEAVES, CTR_POINT_ROUNDS, CTR_BLOSC_ALIASED = range(15)
+N_COUNTERS = 15
 IDX_DEVICE = 0x100  # zgpu_retrieve_elements / zgpu_store_elements flag: the indices are device memory
 POINTS_BITMAP_MAX_BYTES = 16 << 20  # zgpu_retrieve_elements: one bit per leaf of the array
 STORE_EMPTY_CHUNKS = 0x80  # zgpu_store_array_subset flag
@@ -237,7 +237,7 @@ def last_counters() -> dict:
     return {"enc_bytes": buf[0], "zstd_serial": buf[1], "zstd_parallel": buf[2], "blosc_rerun": buf[3],
             "blosc_blocks": buf[4], "zstd_latency": buf[6], "bz2_blocks": buf[7], "bz2_rounds": buf[8],
             "store_decoded": buf[9], "store_encoded": buf[10], "store_carried": buf[11],
-            "point_leaves": buf[12], "point_rounds": buf[13]}
+            "point_leaves": buf[12], "point_rounds": buf[13], "blosc_aliased": buf[14]}
 
 
 def points_chunks(array_shape, chunk_shape, indices) -> list:

@@ -19,7 +19,8 @@
 enum { CTR_ENC_BYTES = 0, CTR_ZSTD_SERIAL = 1, CTR_ZSTD_PARALLEL = 2, CTR_BLOSC_RERUN = 3, CTR_BLOSC_BLOCKS = 4,
        CTR_ITEMS = 5, CTR_ZSTD_LATENCY = 6, CTR_BZ2_BLOCKS = 7, CTR_BZ2_ROUNDS = 8,  // CTR_ITEMS and CTR_BZ2_ROUNDS are host-side
        CTR_STORE_DECODED = 9, CTR_STORE_ENCODED = 10, CTR_STORE_CARRIED = 11,  // the store path's (store.cpp), host-side
-       CTR_POINT_LEAVES = 12, CTR_POINT_ROUNDS = 13, CTR_N = 14 };  // the read by coordinates' (points.cpp), host-side
+       CTR_POINT_LEAVES = 12, CTR_POINT_ROUNDS = 13,  // the read by coordinates' (points.cpp), host-side
+       CTR_BLOSC_ALIASED = 14, CTR_N = 15 };  // alias entries k_zstd_plan wrote for the blosc stage (k_zstd_alias_count)
 // internal ctl slots (not reported): a cached blosc layout was outgrown (the execution is re-run)
 enum { CTR_BLOSC_OVF = 31, CTR_SCRATCH = 30, CTR_ZSTD_NSER = 29, CTR_ZSTD_MAXBLK = 28 };  // not reported (device-side flags / sinks)
 // UnexpectedChunkDecodedSize detail of the last call's first DECODED_SIZE_MISMATCH descriptor

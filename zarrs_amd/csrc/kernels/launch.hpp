@@ -143,6 +143,7 @@ struct ZstdScratch {
   // k_zstd_direct does not copy it into the slot: item bytes [off, off + len) are src[0 .. len).
   // len = 0: none. Byte-shuffled blosc blocks of noisy data: the low-byte plane is a raw block.
   uint64_t *alias = nullptr;
+  unsigned long long *alias_count = nullptr;  // alias entries k_zstd_plan wrote, over all items (nullable; k_zstd_alias_count)
   // the batch's largest block count per item (nullable; zeroed before the call, k_zstd_scan's
   // atomicMax): the record-strided kernels walk n_items x that many records, not x blk_cap
   unsigned long long *max_nblk = nullptr;

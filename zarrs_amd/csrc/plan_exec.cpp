@@ -204,6 +204,7 @@ static void blosc_stage(zgpu_plan &P, const Stage &st, uint8_t *out, hipStream_t
     zstd_bind(D.zs, D.n_sub, D.sub_slot, ZstdWants{!ae || std::atoi(ae) != 0, false, D.zs.knobs},
               [&](int k, uint64_t bytes) { return P.grow(P.blosc.zs[k], bytes); });
     D.zs.counters = P.zstd.zs.counters;
+    D.zs.alias_count = P.d_counter + CTR_BLOSC_ALIASED;
     D.zs.max_nblk = P.zstd.zs.max_nblk;
     D.zs.ser_count = P.zstd.zs.ser_count;
     D.zs.launch_serial = P.zstd.zs.launch_serial;
