@@ -308,7 +308,10 @@ int zgpu_plan_create(zgpu_chain *chain, uint32_t ndim, const zgpu_chunk_desc *de
 int zgpu_plan_execute(zgpu_plan *plan, void *out, int32_t *status, void *hip_stream);
 /* Wait for the plan's last execute on hip_stream and return its per-chunk statuses (first non-zero
  * status as the return value): lets independent plans (e.g. the levels of a multiscale pyramid)
- * run concurrently on separate streams. */
+ * run concurrently on separate streams. A status call is a call of its own for zgpu_last_counters and
+ * zgpu_last_size_mismatch: after it they hold this plan's last execute alone, whichever other plan's
+ * status the thread read before (zgpu_group_status likewise: the group's pieces summed once, the
+ * failing descriptor in the group's status order). */
 int zgpu_plan_status(zgpu_plan *plan, int32_t *status, void *hip_stream);
 void zgpu_plan_destroy(zgpu_plan *plan);
 /* Algorithmic HBM bytes of one execute (encoded bytes read + index bytes + decoded bytes

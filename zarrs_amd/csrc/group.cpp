@@ -201,12 +201,15 @@ int zgpu_group_create(zgpu_chain *const *chains, uint32_t nd, uint32_t n_parts, 
   }
 }
 
+// One call over every piece: the thread's counters are the pieces' sum, and the size-mismatch detail is
+// the first failing piece's, its descriptor named in the group's status order.
 static int group_statuses(zgpu_group *G, int32_t *status) {
   int first_rc = ZGPU_OK;
   std::vector<int32_t> tmp;
+  begin_call();
   for (zgpu_group::Piece &pc : G->pieces) {
     tmp.assign(pc.idx.size(), 0);
-    const int rc = zgpu_plan_status(pc.plan, tmp.data(), G->streams[pc.lane]);
+    const int rc = plan_status_add(pc.plan, tmp.data(), G->streams[pc.lane], pc.idx.data());
     if (rc && !first_rc) first_rc = rc;
     if (status)
       for (size_t i = 0; i < pc.idx.size(); i++) status[pc.idx[i]] = tmp[i];

@@ -30,5 +30,11 @@ hipStream_t ctx_copy_stream(zgpu_ctx *c);
 // subset, or an error status.
 int subset_descs(uint32_t nd, const uint64_t *array_shape, const uint64_t *chunk_shape, const uint64_t *sel_start,
                  const uint64_t *sel_shape, std::vector<zgpu_chunk_desc> &descs, std::vector<uint64_t> &lins);
+// The calling thread's call state (zgpu_last_counters, zgpu_last_size_mismatch) for a call that reads
+// several plans: begin_call clears it once, plan_status_add reads one plan's last execute like
+// zgpu_plan_status and ADDS its counters; the first plan with a size mismatch gives the detail, its
+// descriptor renamed through desc_map (the plan's descriptors in the caller's order; NULL: as they are).
+void begin_call();
+int plan_status_add(zgpu_plan *P, int32_t *status, void *stream, const uint64_t *desc_map);
 
 }  // namespace zgpu

@@ -82,6 +82,21 @@ static zgpu_plan *plan_new(zgpu_chain *ch, uint32_t nd, const zgpu_chunk_desc *d
   return plan_new(ch->ctx, ch->chain, ch->validate, nd, descs, n, out_shape, flags);
 }
 
+void zgpu::begin_call() { reset_call_state(); }
+
+int zgpu::plan_status_add(zgpu_plan *P, int32_t *status, void *stream, const uint64_t *desc_map) {
+  ABI_GUARD_BEGIN
+  if (!P) return set_err(ZGPU_INVALID_ARGUMENT, "NULL argument");
+  std::lock_guard<std::mutex> lk(P->mu);
+  HIPCHK(hipSetDevice(P->ctx->device));
+  const bool had_detail = g_size_detail.valid;
+  const int rc = plan_statuses(*P, status, stream ? (hipStream_t)stream : plan_lane(*P)->stream);
+  if (desc_map && !had_detail && g_size_detail.valid) g_size_detail.desc = desc_map[g_size_detail.desc];
+  if (rc) set_err(rc, zgpu_status_name(rc));
+  return rc;
+  ABI_GUARD_END
+}
+
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
@@ -255,15 +270,11 @@ int zgpu_plan_execute(zgpu_plan *P, void *out, int32_t *status, void *stream) {
   ABI_GUARD_END
 }
 
+// A status call is a call of its own: the thread's counters and size-mismatch detail are this plan's
+// last execute's alone, whatever another plan's status call (or a second one of this plan) left there.
 int zgpu_plan_status(zgpu_plan *P, int32_t *status, void *stream) {
-  ABI_GUARD_BEGIN
-  if (!P) return set_err(ZGPU_INVALID_ARGUMENT, "NULL argument");
-  std::lock_guard<std::mutex> lk(P->mu);
-  HIPCHK(hipSetDevice(P->ctx->device));
-  const int rc = plan_statuses(*P, status, stream ? (hipStream_t)stream : plan_lane(*P)->stream);
-  if (rc) set_err(rc, zgpu_status_name(rc));
-  return rc;
-  ABI_GUARD_END
+  reset_call_state();
+  return plan_status_add(P, status, stream, nullptr);
 }
 
 void zgpu_plan_destroy(zgpu_plan *P) {
